@@ -17,8 +17,26 @@ arenas: sweep, sweep + gather to rank 0, sweep + in-place all-gather),
 (``configs4_sharded``: ONE ResNet-50 INT4 + clip list of >= 2 GiB held by rank 0,
 scattered, swept and gathered, with its oracle parity counts).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N     (one process per GPU, RCCL)
+
+A plain run does only what the headline needs: it builds the list, pre-warms,
+warms up, times the K steps, writes the outputs if ``--dump-outputs DIR`` is
+given and prints the line.  ``--full`` adds every other leg after the timed
+steps (parity of the timed outputs and of the pipeline, the ceiling probe, the
+CPU baselines, the secondary and single-model configs, the pipeline and CLE
+timings, GPU telemetry, and at N > 1 the gathers, weak scaling and
+``configs4_sharded``); ``--no-pipeline``, ``--no-secondary``, ``--no-parity``,
+``--no-sharded`` and ``--cpu-seconds`` trim those legs and mean nothing without
+it.  A leg that did not run is ``null`` in the line.
+
+``--dump-outputs DIR`` writes what the last timed step left in this rank's
+outputs as ``DIR/<field>.npy`` (float32; ``<field>_rank<r>.npy`` at N > 1):
+``dq``, ``codes``, ``scale``, ``zero`` and ``esum``, each the layers' arrays
+flattened and joined in list order.  A field of more than 2^21 elements is
+written as a fixed sample of its elements (seeded by the field's length alone, so
+two runs with the same arguments write the same positions); inputs come from one
+seeded generator and are the same from run to run.
 
 ``python bench.py --gpus N`` with N > 1 and no torchrun environment starts
 torchrun as a CHILD process (``--nproc-per-node N``, 127.0.0.1) before anything
@@ -57,6 +75,13 @@ def parse(argv=None):
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--model", default="mobilenetv2", choices=["mobilenetv2", "resnet50", "deeplab"])
     p.add_argument("--copies", type=int, default=0, help="weight sets in the layer list (0: enough for >= 2 GiB)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also run every other leg (parity checks, ceiling probe, CPU "
+                        "baselines, secondary / single-model configs, pipeline and CLE timings, telemetry, the "
+                        "N > 1 gathers); off: the headline only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs (dq, codes, scale, zero, esum) as DIR/<field>.npy "
+                        "(float32; a fixed seeded sample of a field longer than 2^21 elements)")
     p.add_argument("--bits", type=int, default=8)
     p.add_argument("--granularity", default="channel", choices=["channel", "tensor"])
     p.add_argument("--asym", action="store_true", help="asymmetric (reference default) instead of symmetric")
@@ -1046,6 +1071,46 @@ def probe_ranks(args):
         print(json.dumps({"probe_ranks": rows, "n_gpus": world, "backend": backend}), flush=True)
 
 
+DUMP_FIELDS = ("dq", "codes", "scale", "zero", "esum")
+DUMP_MAX_ELEMS = 1 << 21   # per field: 5 fields x 8 MiB of float32 at the most
+
+
+def dump_outputs(out_dir, layers, dev, rank=0, world=1):
+    """--dump-outputs: the timed path's outputs as they stand after the last timed
+    step, one float32 ``<field>.npy`` per output field (``<field>_rank<r>.npy`` at
+    N > 1, this rank's layers).  ``layers`` holds one (dq, codes, scale, zero, esum)
+    tuple of device tensors per layer (None where the configuration has no such
+    output); a field is its layers' arrays flattened and joined in list order.
+    A field longer than DUMP_MAX_ELEMS is sampled: the sorted distinct values of
+    DUMP_MAX_ELEMS positions drawn by a numpy generator seeded with the field's
+    length, so the same arguments give the same positions in every run and build.
+    int8 / uint8 / int16 codes are exact in float32."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    if torch.device(dev).type == "cuda":
+        torch.cuda.synchronize(dev)
+    for f, name in enumerate(DUMP_FIELDS):
+        flat = [lay[f].reshape(-1) for lay in layers if lay[f] is not None]
+        if not flat:
+            continue
+        ends = np.cumsum([t.numel() for t in flat])
+        total = int(ends[-1])
+        if total <= DUMP_MAX_ELEMS:
+            got = torch.cat([t.to(torch.float32) for t in flat])
+        else:
+            pos = np.unique(np.random.default_rng(total).integers(0, total, DUMP_MAX_ELEMS))
+            cut = np.searchsorted(pos, ends)            # layer j holds pos[cut[j-1]:cut[j]]
+            pos_dev = torch.from_numpy(pos).to(dev)
+            parts, lo, start = [], 0, 0
+            for t, hi, end in zip(flat, cut.tolist(), ends.tolist()):
+                if hi > lo:
+                    parts.append(t[pos_dev[lo:hi] - start].to(torch.float32))
+                lo, start = hi, end
+            got = torch.cat(parts)
+        np.save(out_dir / (f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"), got.cpu().numpy())
+
+
 def _side_leg(fn):
     """A secondary measurement after the timed step: its exception (on this rank)
     becomes {"error": ...} in the JSON line instead of ending the run before rank 0
@@ -1063,6 +1128,9 @@ def _side_leg(fn):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = parse(argv)
+    if not args.full:   # a plain run: the headline alone, every other leg off
+        args.no_parity = args.no_pipeline = args.no_secondary = args.no_sharded = True
+        args.cpu_seconds = 0.0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process per GPU: torchrun as a child, started before any GPU call here
         return launch_ranks(args.gpus, argv)
@@ -1074,8 +1142,13 @@ def main(argv=None):
     if world > 1:
         import torch.distributed as dist
         check_world(args, dist.get_world_size())
-    telemetry = Telemetry(dev)
-    tele_start = telemetry.sample("process_start")
+    full = args.full
+    telemetry = Telemetry(dev) if full else None
+
+    def tele_sample(tag):
+        return telemetry.sample(tag) if telemetry is not None else None
+
+    tele_start = tele_sample("process_start")
     shapes = model_shapes(args.model)
     per_copy = sum(int(torch.Size(s).numel()) for s in shapes)
     copies = args.copies or max(1, -(-(2 << 30) // (4 * per_copy)))   # >= 2 GiB of fp32 weights per rank
@@ -1107,15 +1180,15 @@ def main(argv=None):
         plan = _plan_of(items)
         st = plan.stats
         run = lambda: plan.execute(stream)   # noqa: E731
-    tele = [telemetry.sample("before_prewarm")]
+    tele = [tele_sample("before_prewarm")]
     warm = prewarm(run, stream, dev, args.prewarm_ms) if args.prewarm_ms > 0 else None
-    tele.append(telemetry.sample("after_prewarm"))
+    tele.append(tele_sample("after_prewarm"))
     warm_steps = steps_with_events(run, stream, args.warmup) if args.warmup > 0 else []
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(dev)
-    tele.append(telemetry.sample("before_timed"))
+    tele.append(tele_sample("before_timed"))
     step_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                for _ in range(args.steps)]
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1131,7 +1204,7 @@ def main(argv=None):
         dist.barrier()
     torch.cuda.synchronize(dev)
     wall = time.perf_counter() - t0
-    tele.append(telemetry.sample("after_timed"))
+    tele.append(tele_sample("after_timed"))
     step_ms = [a.elapsed_time(b) for a, b in step_ev]
     dev_ms = ev0.elapsed_time(ev1)          # device time of this rank's K launches on this stream
     t_step = D.max_over_ranks(wall, dev) / args.steps
@@ -1146,6 +1219,11 @@ def main(argv=None):
         dist.all_reduce(lt)
         rank_launch_ms = [round(float(x), 4) for x in lt[0].tolist()]
         rank_algo = [int(x) for x in lt[1].tolist()]
+    if args.dump_outputs:   # what the last timed step left in this rank's outputs
+        outs = items if items is not None else [sw.outputs(i) for i in mine]
+        dump_outputs(args.dump_outputs, [(o.dst if items is not None else o.dq, o.codes, o.scale, o.zero, o.esum)
+                                         for o in outs], dev, rank, world)
+        del outs
     # parity of what was just timed: this rank's layers of the list's first, middle
     # and last weight sets vs the C oracle on the same input tensors (every field)
     timed_parity = None
@@ -1168,7 +1246,7 @@ def main(argv=None):
     del sw, plan, run, items
     torch.cuda.empty_cache()
     gathers = weak = None
-    if world > 1:   # the side legs after the timed step: a failure is reported in the line, not fatal
+    if world > 1 and full:   # the side legs after the timed step: a failure is reported in the line, not fatal
         gloo = dist.get_backend() == "gloo"   # a one-GPU rehearsal stages every transfer through the host
         gathers = _side_leg(lambda: sharded_gathers(specs, dev, stream, reps=2 if gloo else 10))
         weak = _side_leg(lambda: weak_scaling(specs, per_copy * copies, dev, stream, rank, world, args.steps,
@@ -1215,7 +1293,7 @@ def main(argv=None):
         # the same-mix probe last: a ResNet-50 x22 list allocated into the blocks its
         # ~7 GB of probe buffers left ran 0.699 of peak against 0.770 before it in the
         # same process (scripts/r50_state.py; DESIGN.md 3.1 "ResNet-50 in the bench")
-        probe = _side_leg(lambda: same_mix_probe(per_copy * copies, dev, stream))
+        probe = _side_leg(lambda: same_mix_probe(per_copy * copies, dev, stream)) if full else None
         probe_stream, probe_lds = probe if isinstance(probe, tuple) else (probe, probe)
         torch.cuda.empty_cache()
         cpu = _side_leg(lambda: cpu_baseline(args, shapes, args.cpu_seconds)) \
@@ -1307,9 +1385,9 @@ def main(argv=None):
                 "note": "HIP events around each execute() on the launch stream (device ms); prewarm = the "
                         "time-based sweep steps run before the counted warm-up (a fresh lease starts at idle "
                         "clocks), not part of the timed steps",
-                "telemetry": [tele_start] + tele + [telemetry.sample("end_of_bench")],
+                "telemetry": [tele_start] + tele + [tele_sample("end_of_bench")] if full else None,
             },
-            "memory_pattern_probe": {
+            "memory_pattern_probe": None if not full else {
                 "lds_dma_GBs": probe_lds, "vgpr_stream_GBs": probe_stream,
                 "note": "the sweep's read 4 B / write 9 B per element pattern without arithmetic, on this box after "
                         "the timed steps.  NOT a ceiling: box to box it lands 5.2-6.5 TB/s, sometimes below the "

@@ -9,7 +9,7 @@ R=$(pwd)
 out=$R/gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
-A="--steps 10 --warmup 3 --cpu-seconds 0 --no-pipeline --no-secondary --no-parity"
+A="--full --steps 10 --warmup 3 --cpu-seconds 0 --no-pipeline --no-secondary --no-parity"
 timeout -k 10 200 python3 bench.py $A > "$out/plain.log" 2>&1 || { echo "bench rc=$?"; tail -5 "$out/plain.log"; exit 1; }
 python3 -c "
 import json,sys

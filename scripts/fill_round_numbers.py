@@ -1,5 +1,5 @@
 """Fill README.md / DESIGN.md's R05_* placeholders from a bench log (the last
-JSON line of `python bench.py`): python scripts/fill_round_numbers.py <bench.log>"""
+JSON line of `python bench.py --full`): python scripts/fill_round_numbers.py <bench.log>"""
 import json
 import re
 import sys

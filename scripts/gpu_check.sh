@@ -15,4 +15,4 @@ step() {  # name, seconds, command...
 }
 step pytest_gpu ${PYTEST_SECS:-900} python -m pytest tests -m gpu -q -p no:cacheprovider ${PYTEST_ARGS:-}
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 600 python bench.py --steps ${BENCH_STEPS:-20} --warmup 3 --cpu-seconds ${CPU_SECS:-3}
+step bench 600 python bench.py --full --steps ${BENCH_STEPS:-20} --warmup 3 --cpu-seconds ${CPU_SECS:-3}

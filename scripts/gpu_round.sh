@@ -11,7 +11,7 @@ out=gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
 if [ "${BENCH:-1}" = "1" ]; then
-  timeout -k 10 420 python -u bench.py --steps 20 --warmup 5 > "$out/bench.log" 2>&1 \
+  timeout -k 10 420 python -u bench.py --full --steps 20 --warmup 5 > "$out/bench.log" 2>&1 \
       || { echo "bench failed rc=$?"; tail -30 "$out/bench.log"; exit 1; }
   tail -c 600 "$out/bench.log"
 fi

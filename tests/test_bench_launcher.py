@@ -93,7 +93,7 @@ def test_bench_two_ranks_one_gpu():
     oracle with 0 mismatches and both ranks holding checked layers; the gathers,
     weak scaling and configs[4]'s sharded list beside it."""
     r = subprocess.run([sys.executable, "-u", str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--no-secondary", "--no-pipeline", "--prewarm-ms", "50"],
+                        "--full", "--no-secondary", "--no-pipeline", "--prewarm-ms", "50"],
                        capture_output=True, text=True, timeout=600, env=_env(OMP_NUM_THREADS="4"), cwd=str(ROOT))
     print(r.stderr[-3000:])
     assert r.returncode == 0, r.stderr[-3000:]
