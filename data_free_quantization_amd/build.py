@@ -16,7 +16,10 @@ PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libdfq_hip.so"
-SOURCES = ["dfq_lib.hip", "dfq_sweep.hip", "dfq_transform.hip", "dfq_cle.hip", "dfq_cle_relation.hip"]
+# *.hip: device + host code for gfx950.  *.cpp: host-only code, compiled as plain
+# C++ (the CLE loop's planner, which also builds on its own for its sanitizer test).
+SOURCES = ["dfq_lib.hip", "dfq_sweep.hip", "dfq_transform.hip", "dfq_cle.hip", "dfq_cle_relation.hip",
+           "dfq_cle_plan.cpp"]
 # Diagnostics build (bench.py's ceiling probes, scripts/ A/B runs): the same
 # sources with -DDFQ_DIAGNOSTICS (the sweep's A/B variants and environment
 # switches) plus the probes (include/dfq_diag.h).  Never loaded by the product path.
@@ -36,6 +39,9 @@ FLAGS = [
     # (libdfq_hip.so and libdfq_diag.so loaded together must not interpose)
     "-fvisibility=hidden", "-fvisibility-inlines-hidden",
 ]
+# the same without the offload: hipcc takes a .cpp for HIP unless told otherwise
+# (the planner's placement compares doubles: -ffp-contract=off here too)
+HOST_FLAGS = ["-x", "c++"] + [f for f in FLAGS if "offload-arch" not in f and "-fhip-" not in f]
 
 
 def hipcc() -> str:
@@ -53,15 +59,16 @@ def _stale(out: Path, deps) -> bool:
 
 
 def _build_one(out: Path, sources, defines, force: bool, verbose: bool) -> Path:
-    deps = [CSRC / s for s in sources] + [CSRC / "dfq_common.h", CSRC / "dfq_cle_common.h", ROOT / "include" / "dfq_hip.h",
-                                          ROOT / "include" / "dfq_diag.h", EXPORTS, Path(__file__)]
+    deps = [CSRC / s for s in sources] + [CSRC / "dfq_common.h", CSRC / "dfq_cle_common.h", CSRC / "dfq_cle_plan.h",
+                                          ROOT / "include" / "dfq_hip.h", ROOT / "include" / "dfq_diag.h", EXPORTS,
+                                          Path(__file__)]
     if not force and not _stale(out, deps):
         return out
     tag = out.stem
     objs, cmds = [], []
     for s in sources:
         obj = CSRC / f"{Path(s).stem}.{tag}.o"
-        cmds.append([hipcc(), *FLAGS, *defines, "-I", str(ROOT / "include"), "-I", str(CSRC), "-c", str(CSRC / s),
+        cmds.append([hipcc(), *(HOST_FLAGS if s.endswith(".cpp") else FLAGS), *defines, "-I", str(ROOT / "include"), "-I", str(CSRC), "-c", str(CSRC / s),
                      "-o", str(obj)])
         objs.append(str(obj))
     if verbose:

@@ -7,6 +7,10 @@
 // evaluated on the device.  The host enqueues iterations and polls the stop
 // rule's word in pinned memory.  One relation at a time: dfq_cle_relation.hip.
 // fp32 arithmetic is ordered exactly as the reference's torch CPU ops.
+// This file: the kernels, the plan's device tables and the host runtime (device
+// context, pools, run / launch / join).  The planner -- chains, tasks, metric
+// chunks, placement, the structure cache and its checker -- is host-only code in
+// dfq_cle_plan.cpp; dfq_cle_plan.h holds the records and constants both share.
 #include "dfq_cle_common.h"
 
 #include <algorithm>
@@ -18,13 +22,11 @@
 #include <cstring>
 #include <condition_variable>
 #include <functional>
-#include <list>
 #include <memory>
 #include <mutex>
 #include <thread>
 #include <unordered_map>
 #include <new>
-#include <numeric>
 #include <vector>
 
 using namespace dfq;
@@ -33,55 +35,6 @@ using namespace dfq;
 // Device-resident CLE loop (dfq_cle_plan_*)
 // ============================================================================
 namespace dfq {
-
-struct CleRel {
-    float* w1;
-    float* w2;
-    float* b1;
-    float* bnw;
-    float* bnb;
-    float* sacc;
-    int64_t c1, len1, o2, i2, khw2, o2g;
-    int64_t moff;       // this relation's [W1 | W2] range words inside one parity's mins (and maxs)
-    int32_t sacc_init;
-    int32_t vec1;       // W1 rows 16-B aligned (float4 path)
-    int32_t vec2;       // W2 contiguous channel segments 16-B aligned (i2 == 1)
-    int32_t fuse_next;  // >= 0: this relation's W2 is that relation's W1 -- the rescale
-                        // of W2 also produces its row ranges (fused schedule)
-    int32_t dw_prev;    // >= 0: this relation's W1 is that relation's depthwise W2: its W1 row
-                        // ranges are derived (cle_rel_scale) and both run in one launch
-    int32_t w1_self;    // 1: its W1 rescale also writes the next iteration's W1 row ranges
-    int32_t w2_self;    // 1: its depthwise W2 rescale (kApplyDwBoth) writes the next W2 ranges
-};
-
-// Range-launch kinds: W1 rows, W2 contiguous channels (i2 == 1), W2 row tiles
-// (i2 > 1, ordered-uint atomics), reset of the OTHER parity's W2 words.
-// Rescale-launch kinds: W1 elements, W2 elements, per-channel vectors.
-enum : int32_t { kRangeW1 = 0, kRangeW2Contig = 1, kRangeW2Tile = 2, kRangeReset = 3, kRangeResetW1 = 4 };
-enum : int32_t { kApplyW1 = 0, kApplyW2Contig = 1, kApplyW2Tile = 2, kApplyChannels = 3, kApplyDwBoth = 4 };
-
-struct CleTask {
-    int32_t rel;
-    int32_t kind;
-    int64_t a, b;     // rows / channels / elements [a, b)
-    int64_t c0, c1;   // W2 tiles: columns [c0, c1) (one thread each)
-};
-
-struct CleLayer {
-    float* w;
-    float* snap;
-    int64_t n;
-    int64_t nt;   // torch.mean's chunks (1: serial sum)
-};
-
-// One fp32 torch.mean chunk (a thread's share of at::parallel_for in
-// two_pass_reduction): elements [c0, c0 + len) of layer `layer`, slot t.
-struct CleChunk {
-    int32_t layer;
-    int32_t t;
-    int64_t c0;
-    int64_t len;
-};
 
 struct CleState {
     double diff;         // Cross_layer_equal.py `diff`
@@ -96,19 +49,6 @@ struct CleState {
 
 constexpr int kCleW1RowsPerTask = 4;       // one wave per row
 constexpr int kCleW2ChansPerTask = 4;      // one wave per contiguous column
-
-// Short rows (< 64 elements: depthwise filters, the first layers' rows) take a
-// group of G lanes each (G = the next power of two >= the length), 64 / G rows
-// per wave, instead of a whole wave per row -- 4-7x fewer tasks for MobileNetV2's
-// depthwise filters and narrow rows, whose cost is the dependent round trips.
-__host__ __device__ inline int row_group_lanes(int64_t len) {
-    if (len >= 64) return 64;
-    int g = 1;
-    while (g < len) g <<= 1;
-    return g;
-}
-// rows (or channel segments) per task: 4 waves x the rows a wave holds
-__host__ __device__ inline int64_t rows_per_task(int64_t len) { return 4 * (64 / row_group_lanes(len)); }
 
 __device__ __forceinline__ float group_min(float v, int g) {
     for (int off = g >> 1; off >= 1; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
@@ -130,15 +70,6 @@ __device__ __forceinline__ void for_short_rows(int64_t a, int64_t b, int64_t len
         f(c, c < b, sl, G);
     }
 }
-constexpr int64_t kCleChansPerTask = 1024;
-// Rescale tasks hold rows_per_task rows (one per wave).  W1 tasks of short rows
-// (under kCleW1SmallElems elements per task: MobileNetV2's expand convs) take twice
-// that: step 0 of MobileNetV2 had 1,648 W1 tasks of ~2 us in 2,433 blocks, more than
-// are resident, so its last blocks started 8.7 us into the launch
-// (profiles/r06/cle_tl_r06h.log); A/B profiles/r06/cle_ab_rows_r06i.jsonl.
-// Diagnostics switches: DFQ_CLE_W1_ROWS (a fixed factor) / DFQ_CLE_DW_ROWS.
-constexpr int64_t kCleW1SmallElems = 2048, kCleDwRowsMult = 1;
-
 // min / max of n floats at p, one wave, 4 loads in flight per lane
 __device__ __forceinline__ void wave_range(const float* __restrict__ p_, int64_t n, bool vec, int lane, float& vmin,
                                            float& vmax) {
@@ -307,16 +238,8 @@ __device__ __forceinline__ void wave_scale_range(float* __restrict__ p_, int64_t
 // W2 row tiles with KH*KW = khw in (1, kTileMaxKhw] and one group: thread t owns
 // the tile's flattened positions p = t + 256 m (m < khw) -- consecutive threads
 // on consecutive floats, khw independent loads per row in flight -- instead of
-// one thread per column walking its khw floats serially.
-constexpr int kTileMaxKhw = 9;   // 3x3 (and 2x2); larger kernels keep the per-column walk
-// Rows per position-parallel rescale tile (<= kColTileRows): their loads are in
-// flight together (16-row tiles took ~70 us a task on ResNet-50's 3x3 layers,
-// 4-row tiles ~11 us: profiles/r03/cle_tl_*.log)
-#ifndef DFQ_CLE_POS_ROWS   // compile-time A/B (scripts/cle_lib_ab.py builds side by side)
-#define DFQ_CLE_POS_ROWS 4
-#endif
-constexpr int kPosTileMaxRows = DFQ_CLE_POS_ROWS;
-
+// one thread per column walking its khw floats serially (kTileMaxKhw and
+// kPosTileMaxRows, the rows of such a rescale tile: dfq_cle_plan.h).
 __device__ __forceinline__ bool tile_by_position(const CleRel& R, const CleTask& tk) {
     return R.khw2 > 1 && R.khw2 <= kTileMaxKhw && (tk.a / R.o2g) == ((tk.b - 1) / R.o2g);
 }
@@ -948,13 +871,7 @@ __device__ __forceinline__ void cle_apply_body(const CleRel* __restrict__ rels, 
 //     vectors, scalar tail) is one more "tail tile";
 //   * cle_chunk_sum_with: one wave per chunk finishes the cascade in ATen's order
 //     (level 2/3, a0 += a1 += a2 += a3, ILP, lanes, scalar tail).
-constexpr int kCleTile = 8192;            // 32 streams x 16 x 16
-constexpr int kCleTailWords = 64;         // per chunk: 32 stream partials, 24 row-tail, 8 scalar-tail values
-
-struct CleUnit {
-    int32_t chunk;
-    int32_t tile;     // < nb1: full level-1 tile; == nb1: the chunk's tail tile
-};
+// (kCleTile, kCleTailWords and the tile's record CleUnit: dfq_cle_plan.h)
 
 // Before the first iteration, ONE launch instead of six fills, a state upload and
 // the snapshot kernel: both parities' range words armed (mins = 0xFF.., maxs = 0;
@@ -1680,9 +1597,6 @@ static bool cle_timing() {
     static const bool on = ab_env("DFQ_CLE_TIMING") != nullptr;
     return on;
 }
-static double now_us() {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 // Per-device loop stream and pinned state word, shared by every plan of the
 // process (creating and destroying them per call cost ~0.6 ms); plan_run holds
@@ -1777,619 +1691,6 @@ extern "C" int64_t dfq_cle_plan_ws_bytes(const int64_t* target_n, int32_t n_targ
     return b;
 }
 
-// Everything dfq_cle_plan_create derives from the relations' and targets' shapes
-// and tensor identities -- chains, steps, tasks, metric chunks and units, the
-// placement -- but no address: a plan of the same structure reuses it and binds
-// its own tensors (cle_structure_key / the cache in dfq_cle_plan_create).
-struct CleStructure {
-    std::vector<CleRel> R;   // fused / depthwise / self-range flags set (addresses: the first plan's)
-    int64_t M = 0;
-    int32_t chains = 0, steps = 0;
-    bool fused = false;
-    std::vector<CleTask> rt, at;
-    std::vector<int64_t> rstep, astep;
-    int64_t ri0 = 0, ri1 = 0;
-    std::vector<CleLayer> layers;   // n, nt (w / snap bound per plan)
-    std::vector<CleChunk> chunks;
-    std::vector<CleUnit> units;
-    std::vector<int64_t> b1off;
-    int64_t nb1_total = 0;
-    std::vector<int64_t> uoffs, roffs;
-    int32_t nlaunch = 0, stop_off = -1;
-    bool lagged = false;
-    double t_chains = 0, t_tasks = 0, t_chunks = 0, t_place = 0;
-    // algorithmic HBM bytes of one iteration (dfq_cle_plan_stats): the rescales
-    // (8 B per weight element and per channel of each per-channel vector: read +
-    // write; a depthwise pair's filter once), the metric tiles (12 B per target
-    // element: W and the snapshot read, the snapshot written) and the range tasks
-    // that read weights (4 B per element; self ranges are free)
-    int64_t bytes_rescale = 0, bytes_metric = 0, bytes_range = 0;
-    uint64_t id = 0;   // unique per built structure: the device pool remembers whose tables it holds
-};
-static std::atomic<uint64_t> g_struct_ids{0};
-
-static int cle_build_structure(std::vector<CleRel> R, int64_t M, int32_t n_rel, float* const* targets,
-                               const int64_t* target_n, int32_t n_targets, int32_t ref_threads, CleStructure& S) {
-    const double tp1 = now_us();
-    // chains: connected components over the tensors a relation touches
-    std::vector<int32_t> parent(n_rel);
-    std::iota(parent.begin(), parent.end(), 0);
-    auto find = [&](int32_t x) {
-        while (parent[x] != x) x = parent[x] = parent[parent[x]];
-        return x;
-    };
-    for (int32_t a = 0; a < n_rel; ++a) {
-        const void* pa[5] = {R[a].w1, R[a].w2, R[a].b1, R[a].bnw, R[a].bnb};
-        for (int32_t b = 0; b < a; ++b) {
-            const void* pb[5] = {R[b].w1, R[b].w2, R[b].b1, R[b].bnw, R[b].bnb};
-            bool share = false;
-            for (int i = 0; i < 5 && !share; ++i)
-                for (int j = 0; j < 5 && !share; ++j) share = pa[i] && pa[i] == pb[j];
-            if (share) parent[find(a)] = find(b);
-        }
-    }
-    std::vector<int32_t> step_of(n_rel), comp_len(n_rel, 0);
-    int32_t chains = 0, steps = 0;
-    for (int32_t r = 0; r < n_rel; ++r) {
-        const int32_t c = find(r);
-        if (comp_len[c] == 0) ++chains;
-        step_of[r] = comp_len[c]++;
-        steps = std::max(steps, step_of[r] + 1);
-    }
-    // Fused schedule: a relation's W2 must be untouched by the earlier relations of
-    // its chain (its column range can be taken at the start of the iteration), and
-    // its W1 untouched too, or the W2 of the immediately preceding relation -- whose
-    // rescale then produces the W1 row ranges.  Otherwise: per-step range launches.
-    std::vector<int32_t> w1_src(n_rel, -1);
-    bool fused = true;
-    {
-        const char* fe = ab_env("DFQ_CLE_FUSED");   // diagnostics A/B: per-step range launches
-        if (fe && fe[0] == '0') fused = false;
-        std::vector<std::vector<int32_t>> chain_of(n_rel);
-        for (int32_t r = 0; r < n_rel; ++r) chain_of[find(r)].push_back(r);
-        for (const auto& L : chain_of) {
-            for (size_t j = 0; j < L.size() && fused; ++j) {
-                const CleRel& cr = R[L[j]];
-                for (size_t i = 0; i < j && fused; ++i) {
-                    const CleRel& cq = R[L[i]];
-                    if (cq.w1 == cr.w2 || cq.w2 == cr.w2) fused = false;
-                    if (cq.w1 == cr.w1 || cq.w2 == cr.w1) {
-                        const bool ok = i + 1 == j && cq.w2 == cr.w1 && cq.w1 != cr.w1 && w1_src[L[j]] < 0 &&
-                                        (cq.i2 > 1 || cq.o2g == 1) && cr.c1 == cq.o2 && cr.len1 == cq.i2 * cq.khw2;
-                        if (ok) w1_src[L[j]] = L[i];
-                        else fused = false;
-                    }
-                }
-            }
-        }
-        if (fused)
-            for (int32_t r = 0; r < n_rel; ++r)
-                if (w1_src[r] >= 0) R[w1_src[r]].fuse_next = r;
-    }
-    // Depthwise pairs (fused schedule): relation r whose W1 is the depthwise W2 of
-    // the relation q right before it in its chain runs in q's launch: its W1 row
-    // ranges are derived from q's W2 range words (cle_rel_scale), q's filter
-    // rescale and r's W1 rescale become ONE task (kApplyDwBoth), and r no longer
-    // needs W1 range words.  MobileNetV2: 5 rescale launches per iteration -> 3.
-    std::vector<int32_t> dw_next(n_rel, -1);
-    if (fused) {
-        for (int32_t r = 0; r < n_rel; ++r) {
-            const int32_t q = w1_src[r];
-            if (q < 0 || R[q].dw_prev >= 0 || dw_next[q] >= 0) continue;
-            const CleRel& cq = R[q];
-            const CleRel& cr = R[r];
-            const bool dw = cq.i2 == 1 && cq.o2g == 1 && cq.o2 == cq.c1 && cr.c1 == cq.o2 && cr.len1 == cq.khw2;
-            if (!dw) continue;
-            R[r].dw_prev = q;
-            R[q].fuse_next = -1;   // no range words to produce for r's W1
-            dw_next[q] = r;
-        }
-        // steps again: a depthwise-paired relation shares its predecessor's step
-        std::vector<int32_t> cur(n_rel, 0);
-        steps = 0;
-        for (int32_t r = 0; r < n_rel; ++r) {
-            const int32_t c = find(r);
-            step_of[r] = R[r].dw_prev >= 0 ? step_of[R[r].dw_prev] : cur[c]++;
-            steps = std::max(steps, step_of[r] + 1);
-        }
-    }
-    const double tp2 = now_us();
-    // tasks: per-step range + rescale launches, or (fused) one range launch for
-    // every relation's W2 (and untouched W1) followed by the rescale launches
-    std::vector<CleTask> rt, at;
-    std::vector<CleTask>* rout = &rt;   // where the range-task builders emit
-    std::vector<int64_t> rstep(1, 0), astep(1, 0);
-    auto w2_range_tasks = [&](int32_t r) {
-        const CleRel& c = R[r];
-        if (c.i2 == 1) {
-            const int64_t k = rows_per_task(c.o2g * c.khw2);
-            for (int64_t a = 0; a < c.c1; a += k)
-                rout->push_back({r, kRangeW2Contig, a, std::min<int64_t>(a + k, c.c1), 0, 0});
-        } else {
-            for (int64_t a = 0; a < c.o2; a += kColTileRows)
-                for (int64_t i0 = 0; i0 < c.i2; i0 += kThreads)
-                    rout->push_back({r, kRangeW2Tile, a, std::min<int64_t>(a + kColTileRows, c.o2), i0,
-                                     std::min<int64_t>(i0 + kThreads, c.i2)});
-            for (int64_t a = 0; a < c.c1; a += kCleChansPerTask)
-                rout->push_back({r, kRangeReset, a, std::min<int64_t>(a + kCleChansPerTask, c.c1), 0, 0});
-        }
-    };
-    auto w1_range_tasks = [&](int32_t r) {
-        const CleRel& c = R[r];
-        if (c.dw_prev >= 0) return;   // derived from the depthwise predecessor's W2 words
-        if (fused && w1_src[r] >= 0) {   // produced by the previous relation's rescale: reset the next parity
-            for (int64_t a = 0; a < c.c1; a += kCleChansPerTask)
-                rout->push_back({r, kRangeResetW1, a, std::min<int64_t>(a + kCleChansPerTask, c.c1), 0, 0});
-        } else {
-            const int64_t k = rows_per_task(c.len1);
-            for (int64_t a = 0; a < c.c1; a += k)
-                rout->push_back({r, kRangeW1, a, std::min<int64_t>(a + k, c.c1), 0, 0});
-        }
-    };
-    // rows per W1 / depthwise-pair rescale task: rows_per_task (one row per wave)
-    // times a factor (diagnostics A/B: DFQ_CLE_W1_ROWS / DFQ_CLE_DW_ROWS)
-    // 0: the default rule (twice the rows for tasks of short rows, below)
-    const int64_t w1_mult = [] {
-        const char* e = ab_env("DFQ_CLE_W1_ROWS");
-        return e && *e ? std::max<int64_t>(1, atoll(e)) : int64_t(0);
-    }();
-    auto w1_rows = [&](int64_t len1) {
-        const int64_t k = rows_per_task(len1);
-        if (w1_mult > 0) return w1_mult * k;
-        return k * len1 < kCleW1SmallElems ? 2 * k : k;
-    };
-    const int64_t dw_mult = [] {
-        const char* e = ab_env("DFQ_CLE_DW_ROWS");
-        return e && *e ? std::max<int64_t>(1, atoll(e)) : kCleDwRowsMult;
-    }();
-    auto apply_tasks = [&](int32_t r, std::vector<CleTask>& out) {
-        const CleRel& c = R[r];
-        if (c.dw_prev < 0)   // else the predecessor's kApplyDwBoth rescales this W1
-            for (int64_t a = 0, k = w1_rows(c.len1); a < c.c1; a += k)
-                out.push_back({r, kApplyW1, a, std::min<int64_t>(a + k, c.c1), 0, 0});
-        if (dw_next[r] >= 0) {
-            for (int64_t a = 0, k = dw_mult * rows_per_task(c.o2g * c.khw2); a < c.c1; a += k)
-                out.push_back({r, kApplyDwBoth, a, std::min<int64_t>(a + k, c.c1), dw_next[r], 0});
-        } else if (c.i2 == 1) {
-            for (int64_t a = 0, k = rows_per_task(c.o2g * c.khw2); a < c.c1; a += k)
-                out.push_back({r, kApplyW2Contig, a, std::min<int64_t>(a + k, c.c1), 0, 0});
-        } else {
-            // KH*KW > 1 tiles go position-parallel, a row at a time: fewer rows per
-            // task, more tasks in flight (ResNet-50's 3x3 W2 tiles: 16 rows took
-            // ~70 us, DFQ_CLE_TL); 1x1 tiles keep kColTileRows (loads issued together)
-            const int64_t rows = (c.khw2 > 1 && c.khw2 <= kTileMaxKhw) ? kPosTileMaxRows : kColTileRows;
-            for (int64_t a = 0; a < c.o2; a += rows)
-                for (int64_t i0 = 0; i0 < c.i2; i0 += kThreads)
-                    out.push_back({r, kApplyW2Tile, a, std::min<int64_t>(a + rows, c.o2), i0,
-                                   std::min<int64_t>(i0 + kThreads, c.i2)});
-        }
-        // one channel per thread: each channel's scale is a chain of dependent loads
-        // and fp32 divides, and 1,024-channel tasks (4 channels a thread, one after
-        // the other) were the slowest of their steps (6-9 us, DFQ_CLE_TL)
-        for (int64_t a = 0; a < c.c1; a += kThreads)
-            out.push_back({r, kApplyChannels, a, std::min<int64_t>(a + kThreads, c.c1), 0, 0});
-    };
-    int64_t ri0 = 0, ri1 = 0;
-    if (fused) {
-        for (int32_t r = 0; r < n_rel; ++r) {
-            w1_range_tasks(r);
-            w2_range_tasks(r);
-        }
-        rstep.push_back((int64_t)rt.size());
-        // Self ranges: a W1 that no earlier relation of its chain touches is final
-        // once its own row rescale ran, so that task writes the row's next range
-        // (no kRangeW1 task); likewise a depthwise W2 after kApplyDwBoth.  The
-        // first iteration's ranges still come from the full list [rstep0, rstep1);
-        // each iteration's tiles launch runs the rest, [ri0, ri1).
-        for (int32_t r = 0; r < n_rel; ++r) {
-            if (w1_src[r] < 0 && R[r].dw_prev < 0) R[r].w1_self = 1;
-            if (dw_next[r] >= 0) R[r].w2_self = 1;
-        }
-        ri0 = (int64_t)rt.size();
-        for (int64_t t = rstep[0]; t < rstep[1]; ++t) {
-            const CleTask tk = rt[t];
-            if (tk.kind == kRangeW1 && R[tk.rel].w1_self) continue;
-            if (tk.kind == kRangeW2Contig && R[tk.rel].w2_self) continue;
-            rt.push_back(tk);
-        }
-        ri1 = (int64_t)rt.size();
-    }
-    for (int32_t k = 0; k < steps; ++k) {
-        for (int32_t r = 0; r < n_rel; ++r) {
-            if (step_of[r] != k) continue;
-            if (!fused) {
-                w1_range_tasks(r);
-                w2_range_tasks(r);
-            }
-            apply_tasks(r, at);
-        }
-        // The step's slowest tasks first (its span is the last task's end): W2 row
-        // tiles (strided columns, their loads and stores a row at a time), the
-        // per-channel vectors (each a chain of dependent loads), then the depthwise
-        // pairs, W1 rows and contiguous W2 channels (profiles/r03/cle_tl_*.log: tile
-        // tasks started up to 10 us into a step and ran ~10 us)
-        auto prio = [](int32_t kind) {
-            switch (kind) {
-                case kApplyW2Tile: return 0;
-                case kApplyChannels: return 1;
-                case kApplyDwBoth: return 2;
-                case kApplyW1: return 3;
-                default: return 4;
-            }
-        };
-        std::stable_sort(at.begin() + astep.back(), at.end(),
-                         [&](const CleTask& x, const CleTask& y) { return prio(x.kind) < prio(y.kind); });
-        if (!fused) rstep.push_back((int64_t)rt.size());
-        astep.push_back((int64_t)at.size());
-    }
-    const double tp3 = now_us();
-    // metric chunks: torch.mean = sum / n; the sum is two_pass_reduction over
-    // min(threads, ceil(n / 32768)) equal chunks when n >= 32768 (serial below)
-    std::vector<CleLayer> layers(n_targets);
-    std::vector<CleChunk> chunks;
-    std::vector<CleUnit> units;
-    std::vector<int64_t> b1off;
-    int64_t nb1_total = 0;
-    for (int32_t l = 0; l < n_targets; ++l) {
-        const int64_t n = target_n[l];
-        if (!targets[l] || n <= 0) return DFQ_ERR_INVALID;
-        layers[l] = CleLayer{nullptr, nullptr, n, 1};   // the tensor and its snapshot: bound per plan
-        int64_t nt = 1;
-        if (n >= 32768 && ref_threads > 1) nt = std::min<int64_t>(ref_threads, ceil_div(n, (int64_t)32768));
-        layers[l].nt = nt;
-        const int64_t chunk = ceil_div(n, nt);
-        for (int64_t t = 0; t < nt; ++t) {
-            const int64_t b = t * chunk;
-            if (b >= n) break;
-            const int64_t len = std::min<int64_t>(n, b + chunk) - b;
-            const int64_t sz = len / 32;
-            if (aten_ceil_log2(sz) / 4 > 4) return DFQ_ERR_UNSUPPORTED;   // > 16M / chunk
-            const int32_t ci = (int32_t)chunks.size();
-            chunks.push_back(CleChunk{l, (int32_t)t, b, len});
-            const int64_t nb1 = sz / 256;
-            b1off.push_back(32 * nb1_total);   // float offset of this chunk's [nb1][32] level-1 sums
-            nb1_total += nb1;
-            if (len >= 8)
-                for (int64_t g = 0; g <= nb1; ++g) units.push_back(CleUnit{ci, (int32_t)g});
-        }
-    }
-    const double tp4 = now_us();
-    // Placement of the metric tiles and the next iteration's range tasks.  An
-    // iteration group has nlaunch launches: the steps' rescale launches (and, in the
-    // round-4 schedule, one tiles-only launch after them).  Every tile unit and
-    // range task gets an OFFSET in [0, 2 nlaunch): offset k < nlaunch runs in
-    // launch k of its own iteration's group, offset nlaunch + k in launch k of the
-    // next group.  A tensor's tiles and ranges must run after its last rescale of
-    // iteration i and before its first rescale of iteration i + 1: offsets
-    // [last + 1, nlaunch + first - 1].  Resets of a relation's range words go after
-    // that relation's own step and before the next accumulation.
-    // Lagged schedule (nlaunch = steps: no tiles-only launch): the tiles of one
-    // iteration sit in a band of nlaunch - 1 offsets and the stop rule runs as a
-    // block of its own one offset after the band (it reads the chunk sums the
-    // tiles' last arrivals left, after a launch boundary): iteration i's stop rule
-    // runs beside the rescale tasks of iteration i + 1 instead of after a serial
-    // tile -> chunk-combine -> stop-rule chain in a launch of its own, and every
-    // tile of iteration i + 1 starts after it (cle_loop_step_kernel).
-    // MobileNetV2: 4 -> 3 launches per iteration.  Needs the fused range schedule
-    // and no tiny chunks (the stop rule takes their sums from the live weights);
-    // where no band fits (ResNet-50: a tensor rescaled at both steps) or without
-    // lag (DFQ_CLE_LAG=0, diagnostics): the round-4 schedule, everything in the
-    // tiles-only launch and the stop rule at the last tile arrival.
-    const bool tiny = std::any_of(chunks.begin(), chunks.end(), [](const CleChunk& c) { return c.len < 8; });
-    const bool have_tiles = std::any_of(chunks.begin(), chunks.end(), [](const CleChunk& c) { return c.len >= 8; });
-    bool lag_ok = fused && !tiny && have_tiles && steps > 0;
-    if (const char* e = ab_env("DFQ_CLE_LAG")) lag_ok = lag_ok && e[0] != '0';
-    int32_t band_force = -1;   // diagnostics A/B: the tiles' band start
-    // diagnostics A/B: the lagged schedule's stop rule at the last tile arrival
-    // (band of nlaunch offsets) instead of as a block of its own after the band
-    const bool stop_arrival = [] {
-        const char* e = ab_env("DFQ_CLE_STOP");
-        return e && e[0] == 'a';
-    }();
-    if (const char* e = ab_env("DFQ_CLE_BAND")) band_force = atoi(e);
-    // (first, last) step of every tensor the relations rescale: a linear table (a few
-    // hundred tensors at most), looked up once per relation and target layer
-    std::vector<const float*> sp_w;
-    std::vector<std::pair<int32_t, int32_t>> sp_v;
-    auto sp_find = [&](const float* w) -> int32_t {
-        for (size_t i = 0; i < sp_w.size(); ++i)
-            if (sp_w[i] == w) return (int32_t)i;
-        return -1;
-    };
-    std::vector<int32_t> rel_t1(n_rel), rel_t2(n_rel);
-    for (int32_t r = 0; r < n_rel; ++r)
-        for (int side = 0; side < 2; ++side) {
-            const float* w = side ? R[r].w2 : R[r].w1;
-            int32_t i = sp_find(w);
-            if (i < 0) {
-                i = (int32_t)sp_w.size();
-                sp_w.push_back(w);
-                sp_v.push_back({step_of[r], step_of[r]});
-            } else {
-                sp_v[i] = {std::min(sp_v[i].first, step_of[r]), std::max(sp_v[i].second, step_of[r])};
-            }
-            (side ? rel_t2 : rel_t1)[r] = i;
-        }
-    std::vector<int32_t> lay_t(n_targets);
-    for (int32_t l = 0; l < n_targets; ++l) lay_t[l] = lag_ok ? sp_find(targets[l]) : -1;
-    std::vector<int32_t> layer_off(n_targets, 0);
-    int32_t stop_off = -1;   // lagged: the stop rule's own block at this offset (else: the last tile arrival)
-    std::vector<int32_t> rt_off;   // per task of [ri0, ri1)
-    int32_t nlaunch = steps + 1;
-    bool lagged = false;
-    // placement (lagged schedule only): loads in bytes per launch position of a
-    // group -- the steps' rescale traffic, then greedy by size: each range task and
-    // each layer's tiles to the least-loaded admissible offset
-    int32_t lag_max = -1;   // the placement's largest tile offset
-    auto place = [&](int32_t nl_) -> bool {
-        auto window = [&](int32_t ti) -> std::pair<int32_t, int32_t> {   // [lo, hi] offsets (untouched: anywhere)
-            if (ti < 0) return {0, 2 * nl_ - 1};
-            return {sp_v[ti].second + 1, std::min(2 * nl_ - 1, nl_ + sp_v[ti].first - 1)};
-        };
-        std::vector<double> base_load(nl_, 0.0);
-        for (int32_t k = 0; k < steps && k < nl_; ++k)
-            for (int64_t t = astep[k]; t < astep[k + 1]; ++t) {
-                const CleTask& tk = at[t];
-                const CleRel& q = R[tk.rel];
-                double n = 0;
-                if (tk.kind == kApplyW1) n = (double)(tk.b - tk.a) * q.len1;
-                else if (tk.kind == kApplyW2Tile) n = (double)(tk.b - tk.a) * (tk.c1 - tk.c0) * q.khw2;
-                else if (tk.kind != kApplyChannels) n = (double)(tk.b - tk.a) * q.o2g * q.khw2;
-                base_load[k] += 8.0 * n;
-            }
-        // range tasks: their own windows and bytes
-        const int64_t nr = ri1 - ri0;
-        std::vector<std::pair<int32_t, int32_t>> rwin((size_t)nr);
-        std::vector<double> rbytes((size_t)nr);
-        for (int64_t x = 0; x < nr; ++x) {
-            const CleTask& tk = rt[ri0 + x];
-            const CleRel& q = R[tk.rel];
-            std::pair<int32_t, int32_t> w;
-            switch (tk.kind) {
-                case kRangeW1:
-                    w = window(rel_t1[tk.rel]);
-                    rbytes[x] = 4.0 * (tk.b - tk.a) * q.len1;
-                    break;
-                case kRangeW2Contig:
-                    w = window(rel_t2[tk.rel]);
-                    rbytes[x] = 4.0 * (tk.b - tk.a) * q.o2g * q.khw2;
-                    break;
-                case kRangeW2Tile:
-                    w = window(rel_t2[tk.rel]);
-                    rbytes[x] = 4.0 * (tk.b - tk.a) * (tk.c1 - tk.c0) * q.khw2;
-                    break;
-                case kRangeReset:   // after the consumer step, before the next accumulation (>= nl_ + last + 1)
-                    w = {step_of[tk.rel] + 1, std::min(2 * nl_ - 1, nl_ + sp_v[rel_t2[tk.rel]].second)};
-                    rbytes[x] = 64.0;
-                    break;
-                default:            // kRangeResetW1: after the consumer step, before the producer's step two groups on
-                    w = {step_of[tk.rel] + 1, 2 * nl_ - 1};
-                    rbytes[x] = 64.0;
-            }
-            if (w.first > w.second) return false;
-            rwin[x] = w;
-        }
-        // tiles: a band [B0, B0 + nl_ - 2] meeting every layer's window; the stop
-        // rule one offset after the band's last used offset
-        int32_t maxlo = 0, minhi = 2 * nl_ - 1;
-        std::vector<std::pair<int32_t, int32_t>> lwin(n_targets);
-        for (int32_t l = 0; l < n_targets; ++l) {
-            lwin[l] = window(lay_t[l]);
-            if (lwin[l].first > lwin[l].second) return false;
-            maxlo = std::max(maxlo, lwin[l].first);
-            minhi = std::min(minhi, lwin[l].second);
-        }
-        const int32_t bw = stop_arrival ? nl_ : nl_ - 1;   // band width
-        if (bw < 1) return false;
-        const int32_t b_lo = std::max(0, maxlo - bw + 1), b_hi = std::min(minhi, 2 * nl_ - 1 - bw);
-        if (b_lo > b_hi) return false;
-        std::vector<int32_t> lord(n_targets);
-        std::iota(lord.begin(), lord.end(), 0);
-        std::sort(lord.begin(), lord.end(),
-                  [&](int32_t x, int32_t y) { return target_n[x] != target_n[y] ? target_n[x] > target_n[y] : x < y; });
-        std::vector<int64_t> rord((size_t)nr);
-        std::iota(rord.begin(), rord.end(), 0);
-        std::sort(rord.begin(), rord.end(),
-                  [&](int64_t x, int64_t y) { return rbytes[x] != rbytes[y] ? rbytes[x] > rbytes[y] : x < y; });
-        double best = 1e300;
-        std::vector<int32_t> roff((size_t)nr), loff(n_targets);
-        for (int32_t B0 = b_lo; B0 <= b_hi; ++B0) {
-            if (band_force >= 0 && B0 != band_force && band_force >= b_lo && band_force <= b_hi) continue;
-            std::vector<double> load = base_load;
-            auto pick = [&](int32_t lo, int32_t hi, double bytes) {
-                int32_t bo = lo;
-                for (int32_t o = lo; o <= hi; ++o)
-                    if (load[o % nl_] < load[bo % nl_]) bo = o;
-                load[bo % nl_] += bytes;
-                return bo;
-            };
-            for (int64_t x : rord) roff[x] = pick(rwin[x].first, rwin[x].second, rbytes[x]);
-            int32_t maxoff = 0;
-            for (int32_t l : lord) {
-                loff[l] = pick(std::max(lwin[l].first, B0), std::min(lwin[l].second, B0 + bw - 1), 12.0 * target_n[l]);
-                maxoff = std::max(maxoff, loff[l]);
-            }
-            if (!stop_arrival && maxoff + 1 > 2 * nl_ - 1) continue;
-            double cost = *std::max_element(load.begin(), load.end());
-            if (cost < best) {
-                best = cost;
-                layer_off = loff;
-                rt_off = roff;
-                stop_off = stop_arrival ? -1 : maxoff + 1;
-                lag_max = maxoff;
-            }
-        }
-        return best < 1e300;
-    };
-    if (lag_ok && place(steps) && (stop_arrival ? lag_max >= steps : stop_off >= steps)) {
-        nlaunch = steps;
-        lagged = true;
-    } else {   // everything in the tiles-only launch after the steps (offset steps), the stop rule at the last arrival
-        nlaunch = steps + 1;
-        stop_off = -1;
-        layer_off.assign(n_targets, steps);
-        rt_off.assign((size_t)(ri1 - ri0), steps);
-    }
-    std::vector<int64_t> uoffs(2 * nlaunch + 1, 0), roffs(2 * nlaunch + 1, 0);
-    {
-        std::vector<std::vector<CleUnit>> ub(2 * nlaunch);
-        for (const CleUnit& u : units) ub[layer_off[chunks[u.chunk].layer]].push_back(u);
-        units.clear();
-        for (int32_t k = 0; k < 2 * nlaunch; ++k) {
-            uoffs[k] = (int64_t)units.size();
-            units.insert(units.end(), ub[k].begin(), ub[k].end());
-        }
-        uoffs[2 * nlaunch] = (int64_t)units.size();
-        if (fused) {   // (the unfused schedule's range tasks are per step: rstep; roffs stay empty)
-            std::vector<std::vector<CleTask>> rb(2 * nlaunch);
-            for (int64_t t = ri0; t < ri1; ++t) rb[rt_off[t - ri0]].push_back(rt[t]);
-            rt.resize(ri0);
-            for (int32_t k = 0; k < 2 * nlaunch; ++k) {
-                roffs[k] = (int64_t)rt.size();
-                rt.insert(rt.end(), rb[k].begin(), rb[k].end());
-            }
-            roffs[2 * nlaunch] = (int64_t)rt.size();
-            ri1 = (int64_t)rt.size();
-        }
-    }
-    S.R = std::move(R);
-    S.M = M;
-    S.chains = chains;
-    S.steps = steps;
-    S.fused = fused;
-    S.rt = std::move(rt);
-    S.at = std::move(at);
-    S.rstep = std::move(rstep);
-    S.astep = std::move(astep);
-    S.ri0 = ri0;
-    S.ri1 = ri1;
-    S.layers = std::move(layers);
-    S.chunks = std::move(chunks);
-    S.units = std::move(units);
-    S.b1off = std::move(b1off);
-    S.nb1_total = nb1_total;
-    S.uoffs = std::move(uoffs);
-    S.roffs = std::move(roffs);
-    S.nlaunch = nlaunch;
-    S.stop_off = stop_off;
-    S.lagged = lagged;
-    S.id = ++g_struct_ids;
-    for (const CleTask& tk : S.at) {
-        const CleRel& q = S.R[tk.rel];
-        const int64_t n = tk.b - tk.a;
-        switch (tk.kind) {
-            case kApplyW1: S.bytes_rescale += 8 * n * q.len1; break;
-            case kApplyW2Contig:
-            case kApplyDwBoth: S.bytes_rescale += 8 * n * q.o2g * q.khw2; break;
-            case kApplyW2Tile: S.bytes_rescale += 8 * n * (tk.c1 - tk.c0) * q.khw2; break;
-            default:
-                S.bytes_rescale += 8 * n * ((q.b1 ? 1 : 0) + (q.bnw ? 1 : 0) + (q.bnb ? 1 : 0) + (q.sacc ? 1 : 0));
-        }
-    }
-    for (int32_t l = 0; l < n_targets; ++l) S.bytes_metric += 12 * target_n[l];
-    {
-        const int64_t r0 = fused ? S.ri0 : 0, r1 = fused ? S.ri1 : (int64_t)S.rt.size();
-        for (int64_t t = r0; t < r1; ++t) {
-            const CleTask& tk = S.rt[t];
-            const CleRel& q = S.R[tk.rel];
-            const int64_t n = tk.b - tk.a;
-            if (tk.kind == kRangeW1) S.bytes_range += 4 * n * q.len1;
-            else if (tk.kind == kRangeW2Contig) S.bytes_range += 4 * n * q.o2g * q.khw2;
-            else if (tk.kind == kRangeW2Tile) S.bytes_range += 4 * n * (tk.c1 - tk.c0) * q.khw2;
-        }
-    }
-    const double tp5 = now_us();
-    S.t_chains = tp2 - tp1;
-    S.t_tasks = tp3 - tp2;
-    S.t_chunks = tp4 - tp3;
-    S.t_place = tp5 - tp4;
-    return DFQ_OK;
-}
-
-// The structure key: shapes, flags and the identity pattern of every tensor
-// address (which relation / target slots share a tensor), the metric's thread
-// count and the diagnostics library's schedule switches.  Two calls with equal
-// keys get equal structures.
-static std::vector<int64_t> cle_structure_key(const std::vector<CleRel>& R, int64_t M, float* const* targets,
-                                              const int64_t* target_n, int32_t n_targets, int32_t ref_threads) {
-    std::vector<std::pair<uintptr_t, int32_t>> ps;
-    ps.reserve(5 * R.size() + n_targets);
-    for (const CleRel& c : R)
-        for (const void* q : {(const void*)c.w1, (const void*)c.w2, (const void*)c.b1, (const void*)c.bnw,
-                              (const void*)c.bnb})
-            ps.push_back({reinterpret_cast<uintptr_t>(q), (int32_t)ps.size()});
-    for (int32_t l = 0; l < n_targets; ++l) ps.push_back({reinterpret_cast<uintptr_t>(targets[l]), (int32_t)ps.size()});
-    std::vector<int32_t> id(ps.size());
-    std::vector<std::pair<uintptr_t, int32_t>> srt = ps;
-    std::sort(srt.begin(), srt.end());
-    for (size_t i = 0; i < srt.size();) {   // every slot -> the first slot holding the same address
-        size_t j = i;
-        while (j < srt.size() && srt[j].first == srt[i].first) ++j;
-        for (size_t k = i; k < j; ++k) id[srt[k].second] = srt[i].first ? srt[i].second : -1;
-        i = j;
-    }
-    std::vector<int64_t> key;
-    key.reserve(16 * R.size() + 2 * n_targets + 16);
-    key.push_back((int64_t)R.size());
-    key.push_back(M);
-    key.push_back(n_targets);
-    key.push_back(ref_threads);
-    for (const char* sw : {"DFQ_CLE_FUSED", "DFQ_CLE_LAG", "DFQ_CLE_BAND", "DFQ_CLE_STOP",
-                           "DFQ_CLE_W1_ROWS", "DFQ_CLE_DW_ROWS"}) {   // diagnostics library only
-        const char* v = ab_env(sw);
-        int64_t h = v ? 1 : 0;
-        for (int k = 0; v && v[k] && k < 8; ++k) h = h * 131 + (unsigned char)v[k];
-        key.push_back(h);
-    }
-    size_t q = 0;
-    for (const CleRel& c : R) {
-        key.insert(key.end(), {c.c1, c.len1, c.o2, c.i2, c.khw2, (int64_t)c.sacc_init, (int64_t)c.vec1, (int64_t)c.vec2,
-                               (int64_t)(c.sacc != nullptr)});
-        for (int k = 0; k < 5; ++k) key.push_back(id[q++]);
-    }
-    for (int32_t l = 0; l < n_targets; ++l) {
-        key.push_back(target_n[l]);
-        key.push_back(id[q++]);
-    }
-    return key;
-}
-
-// The relations' descriptors as the device's records: shapes checked as
-// dfq_cle_relation; each relation's [W1 | W2] range words at moff (M in all).
-static int cle_rels_from_desc(const dfq_cle_rel* rels, int32_t n_rel, std::vector<CleRel>& R, int64_t& M) {
-    R.assign(n_rel, CleRel{});
-    M = 0;
-    for (int32_t r = 0; r < n_rel; ++r) {
-        const dfq_cle_rel& d = rels[r];
-        if (!d.w1 || !d.w2 || !d.b1 || d.c1 <= 0 || d.len1 <= 0 || d.o2 <= 0 || d.i2 <= 0 || d.khw2 <= 0)
-            return DFQ_ERR_INVALID;
-        int64_t groups = 1;
-        if (d.c1 != d.i2) {
-            groups = d.c1 / d.i2;
-            if (groups <= 0 || groups * d.i2 != d.c1) return DFQ_ERR_SHAPE;
-        }
-        if (d.o2 % groups != 0) return DFQ_ERR_SHAPE;
-        CleRel c{};
-        c.w1 = d.w1; c.w2 = d.w2; c.b1 = d.b1; c.bnw = d.bn_w; c.bnb = d.bn_b; c.sacc = d.s_acc;
-        c.c1 = d.c1; c.len1 = d.len1; c.o2 = d.o2; c.i2 = d.i2; c.khw2 = d.khw2; c.o2g = d.o2 / groups;
-        c.moff = M;
-        c.sacc_init = d.s_acc_init;
-        c.vec1 = (d.len1 % 4 == 0 && reinterpret_cast<uintptr_t>(d.w1) % 16 == 0) ? 1 : 0;
-        c.vec2 = (d.i2 == 1 && (c.o2g * d.khw2) % 4 == 0 && reinterpret_cast<uintptr_t>(d.w2) % 16 == 0) ? 1 : 0;
-        c.fuse_next = -1;
-        c.dw_prev = -1;
-        c.w1_self = 0;
-        c.w2_self = 0;
-        M += 2 * d.c1;
-        R[r] = c;
-    }
-    return DFQ_OK;
-}
-
-static std::mutex g_struct_mu;
-static std::list<std::pair<std::vector<int64_t>, std::shared_ptr<const CleStructure>>> g_struct_cache;
-constexpr size_t kStructCacheCap = 8;
-
 extern "C" int dfq_cle_plan_create(const dfq_cle_rel* rels, int32_t n_rel, float* const* targets,
                                    const int64_t* target_n, int32_t n_targets, double s_min, double s_max,
                                    int32_t is_signed, float eps, int32_t ref_threads, void* ws, int64_t ws_bytes,
@@ -2407,28 +1708,11 @@ extern "C" int dfq_cle_plan_create(const dfq_cle_rel* rels, int32_t n_rel, float
     const double tp1 = now_us();
     // the structure (chains, tasks, chunks, placement) from the cache when a plan of
     // the same shapes and tensor-sharing pattern was built before
-    std::shared_ptr<const CleStructure> S;
     bool cached = false;
-    const std::vector<int64_t> key = cle_structure_key(R, M, targets, target_n, n_targets, ref_threads);
-    {
-        std::lock_guard<std::mutex> lock(g_struct_mu);
-        for (auto it = g_struct_cache.begin(); it != g_struct_cache.end(); ++it)
-            if (it->first == key) {
-                S = it->second;
-                g_struct_cache.splice(g_struct_cache.begin(), g_struct_cache, it);   // most recent first
-                cached = true;
-                break;
-            }
-    }
-    if (!S) {
-        auto built = std::make_shared<CleStructure>();
-        const int rc = cle_build_structure(R, M, n_rel, targets, target_n, n_targets, ref_threads, *built);
-        if (rc != DFQ_OK) return rc;
-        S = built;
-        std::lock_guard<std::mutex> lock(g_struct_mu);
-        g_struct_cache.emplace_front(key, S);
-        if (g_struct_cache.size() > kStructCacheCap) g_struct_cache.pop_back();
-    }
+    int rc = DFQ_OK;
+    const std::shared_ptr<const CleStructure> S =
+        cle_structure_cached(R, M, targets, target_n, n_targets, ref_threads, rc, cached);
+    if (!S) return rc;
     const double tp5 = now_us();
     // this plan's addresses into its copy of the relations and layers
     std::vector<CleRel> Rb = S->R;
@@ -3388,248 +2672,3 @@ hipError_t preload_cle() {   // see dfq_preload
     return e;
 }
 }  // namespace dfq
-
-#ifdef DFQ_DIAGNOSTICS
-#include "dfq_diag.h"   // default visibility for the entry point below
-// ---- diagnostics: the plan structure's index invariants, on the host -----------
-// Builds the structure dfq_cle_plan_create would (chains, tasks, metric chunks and
-// units, the lagged placement) -- host code only, no device memory, so it runs on
-// a machine without a GPU and with stand-in addresses -- and checks every index
-// the step, range, tile, stop-rule and rollback blocks derive from it:
-//  * task tables: step offsets monotone and inside the tables; every task's
-//    relation, rows / channels / columns inside that relation's shapes;
-//  * range words and rollback saves: moff + 2 c1 <= M (both parities' words) and
-//    2 moff + 4 c1 <= 2 M (vsave: b1 | bn_w | bn_b | S per channel);
-//  * metric chunks and units: layer, element span, level-1 slots inside the tables;
-//  * placement: per launch offset the unit / range slices partition the tables;
-//    a tensor's tiles and ranges sit after its last rescale of iteration i and
-//    before its first rescale of iteration i + 1 (its window), range resets after
-//    their relation's step; lagged plans: the stop rule one offset after every tile
-//    of its iteration and before the next iteration's first tile.
-// The round-5 fault of a development tree was in this code's
-// domain; tests/test_cle_structure.py runs it on every zoo model and schedule
-// switch and on fuzzed relation graphs.
-// info[0..7] = steps, nlaunch, lagged, stop_off, rescale tasks, range tasks, units,
-// chunks.  Returns DFQ_OK, or DFQ_ERR_INVALID with the first violation in msg.
-extern "C" int dfq_diag_cle_check_structure(const dfq_cle_rel* rels, int32_t n_rel, float* const* targets,
-                                            const int64_t* target_n, int32_t n_targets, int32_t ref_threads,
-                                            int64_t* info, char* msg, int32_t msg_cap) {
-    auto fail = [&](const char* fmt, long long a, long long b, long long c) {
-        if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, fmt, a, b, c);
-        return DFQ_ERR_INVALID;
-    };
-    if (n_rel < 0 || n_targets < 0 || (n_rel > 0 && !rels) || (n_targets > 0 && (!targets || !target_n)))
-        return fail("bad arguments %lld %lld %lld", n_rel, n_targets, 0);
-    std::vector<CleRel> R0;
-    int64_t M = 0;
-    if (const int rc = cle_rels_from_desc(rels, n_rel, R0, M); rc != DFQ_OK) return rc;
-    CleStructure S;
-    if (const int rc = cle_build_structure(R0, M, n_rel, targets, target_n, n_targets, ref_threads, S); rc != DFQ_OK)
-        return rc;
-    const std::vector<CleRel>& R = S.R;
-    const int32_t steps = S.steps, NL = S.nlaunch;
-    if (const char* e = getenv("DFQ_CLE_PLACE_DUMP"); e && *e) {
-        // per launch offset: blocks and bytes of rescale tasks, metric tiles and range tasks
-        fprintf(stderr, "DFQ_CLE_PLACE steps %d nlaunch %d lagged %d stop_off %d\n", steps, NL, (int)S.lagged,
-                S.stop_off);
-        for (int32_t k = 0; k < 2 * NL; ++k) {
-            int64_t na = 0;
-            double ba = 0;
-            if (k < steps)
-                for (int64_t t = S.astep[k]; t < S.astep[k + 1]; ++t, ++na) {
-                    const CleTask& tk = S.at[t];
-                    const CleRel& q = R[tk.rel];
-                    const int64_t n = tk.b - tk.a;
-                    if (tk.kind == kApplyW1) ba += 8.0 * n * q.len1;
-                    else if (tk.kind == kApplyW2Tile) ba += 8.0 * n * (tk.c1 - tk.c0) * q.khw2;
-                    else if (tk.kind != kApplyChannels) ba += 8.0 * n * q.o2g * q.khw2;
-                }
-            double bu = 0;
-            for (int64_t u = S.uoffs[k]; u < S.uoffs[k + 1]; ++u) {
-                const CleChunk& ch = S.chunks[S.units[u].chunk];
-                const int64_t nb1 = ch.len / kCleTile;
-                bu += 12.0 * (S.units[u].tile < nb1 ? kCleTile : ch.len - nb1 * kCleTile);
-            }
-            double br = 0;
-            for (int64_t t = S.roffs[k]; t < S.roffs[k + 1]; ++t) {
-                const CleTask& tk = S.rt[t];
-                const CleRel& q = R[tk.rel];
-                const int64_t n = tk.b - tk.a;
-                if (tk.kind == kRangeW1) br += 4.0 * n * q.len1;
-                else if (tk.kind == kRangeW2Contig) br += 4.0 * n * q.o2g * q.khw2;
-                else if (tk.kind == kRangeW2Tile) br += 4.0 * n * (tk.c1 - tk.c0) * q.khw2;
-            }
-            fprintf(stderr, "DFQ_CLE_PLACE offset %d: rescale %lld blocks %.2f MB, tiles %lld blocks %.2f MB, ranges %lld blocks %.2f MB\n",
-                    k, (long long)na, ba / 1e6, (long long)(S.uoffs[k + 1] - S.uoffs[k]), bu / 1e6,
-                    (long long)(S.roffs[k + 1] - S.roffs[k]), br / 1e6);
-        }
-    }
-    if (info) {
-        const int64_t v[8] = {steps, NL, S.lagged ? 1 : 0, S.stop_off, (int64_t)S.at.size(), (int64_t)S.rt.size(),
-                              (int64_t)S.units.size(), (int64_t)S.chunks.size()};
-        std::memcpy(info, v, sizeof(v));
-    }
-    // relations: range words and rollback saves inside their tables, links valid
-    for (int32_t r = 0; r < n_rel; ++r) {
-        const CleRel& c = R[r];
-        if (c.moff < 0 || c.moff + 2 * c.c1 > S.M) return fail("rel %lld: range words [%lld, +2 c1) past M %lld", r, c.moff, S.M);
-        if (2 * c.moff + 4 * c.c1 > 2 * S.M) return fail("rel %lld: rollback saves past 2 M (moff %lld, c1 %lld)", r, c.moff, c.c1);
-        if (c.fuse_next >= n_rel || c.dw_prev >= n_rel || c.fuse_next < -1 || c.dw_prev < -1)
-            return fail("rel %lld: link out of range (fuse_next %lld, dw_prev %lld)", r, c.fuse_next, c.dw_prev);
-        if (c.fuse_next >= 0 && R[c.fuse_next].moff + R[c.fuse_next].c1 > S.M)
-            return fail("rel %lld: fused W1 words of rel %lld past M %lld", r, c.fuse_next, S.M);
-    }
-    // rescale tasks per step
-    if ((int32_t)S.astep.size() != steps + 1 || S.astep[0] != 0 || S.astep.back() != (int64_t)S.at.size())
-        return fail("astep: %lld entries for %lld steps, last %lld", (long long)S.astep.size(), steps,
-                    S.astep.empty() ? -1 : S.astep.back());
-    std::vector<int32_t> rel_step(n_rel, -1);
-    std::vector<std::pair<const float*, int32_t>> touch;   // (tensor, step) of every weight rescale
-    for (int32_t k = 0; k < steps; ++k) {
-        if (S.astep[k + 1] < S.astep[k]) return fail("astep not monotone at step %lld: %lld > %lld", k, S.astep[k], S.astep[k + 1]);
-        for (int64_t t = S.astep[k]; t < S.astep[k + 1]; ++t) {
-            const CleTask& tk = S.at[t];
-            if (tk.rel < 0 || tk.rel >= n_rel) return fail("rescale task %lld: relation %lld of %lld", t, tk.rel, n_rel);
-            const CleRel& c = R[tk.rel];
-            if (tk.a < 0 || tk.a >= tk.b) return fail("rescale task %lld: empty or negative span [%lld, %lld)", t, tk.a, tk.b);
-            switch (tk.kind) {
-                case kApplyW1:
-                    if (tk.b > c.c1) return fail("W1 task %lld: rows to %lld of %lld", t, tk.b, c.c1);
-                    touch.push_back({c.w1, k});
-                    break;
-                case kApplyW2Contig:
-                    if (tk.b > c.c1 || c.i2 != 1) return fail("W2 contig task %lld: channels to %lld of %lld", t, tk.b, c.c1);
-                    touch.push_back({c.w2, k});
-                    break;
-                case kApplyDwBoth:
-                    if (tk.b > c.c1 || tk.c0 < 0 || tk.c0 >= n_rel || R[tk.c0].w1 != c.w2 || R[tk.c0].dw_prev != tk.rel)
-                        return fail("depthwise pair task %lld: partner %lld, channels to %lld", t, tk.c0, tk.b);
-                    touch.push_back({c.w2, k});
-                    break;
-                case kApplyW2Tile:
-                    if (tk.b > c.o2 || tk.c0 < 0 || tk.c0 >= tk.c1 || tk.c1 > c.i2)
-                        return fail("W2 tile task %lld: rows to %lld, columns to %lld", t, tk.b, tk.c1);
-                    touch.push_back({c.w2, k});
-                    break;
-                case kApplyChannels:
-                    if (tk.b > c.c1) return fail("channel task %lld: channels to %lld of %lld", t, tk.b, c.c1);
-                    if (rel_step[tk.rel] >= 0 && rel_step[tk.rel] != k)
-                        return fail("relation %lld: channel tasks in steps %lld and %lld", tk.rel, rel_step[tk.rel], k);
-                    rel_step[tk.rel] = k;
-                    break;
-                default:
-                    return fail("rescale task %lld: kind %lld", t, tk.kind, 0);
-            }
-        }
-    }
-    for (int32_t r = 0; r < n_rel; ++r)
-        if (rel_step[r] < 0) return fail("relation %lld has no channel task", r, 0, 0);
-    // range tasks
-    const int64_t nrt = (int64_t)S.rt.size();
-    if (S.ri0 < 0 || S.ri0 > S.ri1 || S.ri1 > nrt) return fail("range slice [%lld, %lld) of %lld tasks", S.ri0, S.ri1, nrt);
-    for (int64_t t = 0; t < nrt; ++t) {
-        const CleTask& tk = S.rt[t];
-        if (tk.rel < 0 || tk.rel >= n_rel) return fail("range task %lld: relation %lld of %lld", t, tk.rel, n_rel);
-        const CleRel& c = R[tk.rel];
-        if (tk.a < 0 || tk.a >= tk.b) return fail("range task %lld: span [%lld, %lld)", t, tk.a, tk.b);
-        const bool ok = tk.kind == kRangeW2Tile ? (tk.b <= c.o2 && tk.c0 >= 0 && tk.c0 < tk.c1 && tk.c1 <= c.i2)
-                                                : (tk.kind >= kRangeW1 && tk.kind <= kRangeResetW1 && tk.b <= c.c1);
-        if (!ok) return fail("range task %lld (kind %lld): span to %lld out of the relation's shape", t, tk.kind, tk.b);
-    }
-    // metric chunks and units
-    int64_t nb1_seen = 0;
-    for (size_t ci = 0; ci < S.chunks.size(); ++ci) {
-        const CleChunk& ch = S.chunks[ci];
-        if (ch.layer < 0 || ch.layer >= n_targets) return fail("chunk %lld: layer %lld of %lld", (long long)ci, ch.layer, n_targets);
-        if (ch.c0 < 0 || ch.len <= 0 || ch.c0 + ch.len > target_n[ch.layer])
-            return fail("chunk %lld: elements [%lld, +%lld) past its layer", (long long)ci, ch.c0, ch.len);
-        const int64_t nb1 = ch.len / 32 / 256;
-        if (S.b1off[ci] != 32 * nb1_seen) return fail("chunk %lld: level-1 offset %lld, expected %lld", (long long)ci, S.b1off[ci], 32 * nb1_seen);
-        nb1_seen += nb1;
-    }
-    if (nb1_seen != S.nb1_total) return fail("level-1 slots %lld, table %lld", nb1_seen, S.nb1_total, 0);
-    for (size_t u = 0; u < S.units.size(); ++u) {
-        const CleUnit& un = S.units[u];
-        if (un.chunk < 0 || un.chunk >= (int32_t)S.chunks.size()) return fail("unit %lld: chunk %lld", (long long)u, un.chunk, 0);
-        const CleChunk& ch = S.chunks[un.chunk];
-        if (ch.len < 8 || un.tile < 0 || un.tile > ch.len / 32 / 256)
-            return fail("unit %lld: tile %lld of chunk %lld", (long long)u, un.tile, un.chunk);
-        // cle_tiles_body's element ranges: a full tile is 8,192 elements inside the
-        // chunk; a tail tile's [e0, len) (empty when 8,192 divides the chunk) fits the
-        // LDS staging area below the b0 sums
-        const int64_t nb1 = ch.len / 32 / 256, e0 = (int64_t)un.tile * kCleTile;
-        if (un.tile < nb1 ? e0 + kCleTile > ch.len : (ch.len - e0 < 0 || ch.len - e0 > kCleTile + kCleTailWords))
-            return fail("unit %lld: tile past chunk %lld (len %lld)", (long long)u, un.chunk, ch.len);
-    }
-    // placement tables
-    if ((int32_t)S.uoffs.size() != 2 * NL + 1 || S.uoffs[0] != 0 || S.uoffs.back() != (int64_t)S.units.size())
-        return fail("uoffs: %lld entries for %lld launches, last %lld", (long long)S.uoffs.size(), NL, S.uoffs.back());
-    for (int32_t k = 0; k < 2 * NL; ++k)
-        if (S.uoffs[k + 1] < S.uoffs[k]) return fail("uoffs not monotone at %lld", k, 0, 0);
-    if (S.fused) {
-        if ((int32_t)S.roffs.size() != 2 * NL + 1 || S.roffs[0] != S.ri0 || S.roffs.back() != S.ri1)
-            return fail("roffs: %lld entries, [%lld, %lld)", (long long)S.roffs.size(), S.roffs.empty() ? -1 : S.roffs[0],
-                        S.roffs.empty() ? -1 : S.roffs.back());
-        for (int32_t k = 0; k < 2 * NL; ++k)
-            if (S.roffs[k + 1] < S.roffs[k]) return fail("roffs not monotone at %lld", k, 0, 0);
-    } else if ((int32_t)S.rstep.size() != steps + 1 || S.rstep.back() != nrt) {
-        return fail("unfused rstep: %lld entries, last %lld of %lld", (long long)S.rstep.size(), S.rstep.back(), nrt);
-    }
-    if (NL != (S.lagged ? steps : steps + 1)) return fail("nlaunch %lld for %lld steps (lagged %lld)", NL, steps, S.lagged);
-    // windows: a tensor's first / last rescale step
-    auto span = [&](const float* w, int32_t& first, int32_t& last) {
-        first = INT32_MAX;
-        last = -1;
-        for (const auto& x : touch)
-            if (x.first == w) {
-                first = std::min(first, x.second);
-                last = std::max(last, x.second);
-            }
-        return last >= 0;
-    };
-    auto in_window = [&](const float* w, int32_t o) {
-        int32_t f, l;
-        if (!span(w, f, l)) return o >= 0 && o <= 2 * NL - 1;
-        return o >= l + 1 && o <= std::min(2 * NL - 1, NL + f - 1);
-    };
-    int32_t umin = INT32_MAX, umax = -1;
-    for (int32_t k = 0; k < 2 * NL; ++k)
-        for (int64_t u = S.uoffs[k]; u < S.uoffs[k + 1]; ++u) {
-            const int32_t l = S.chunks[S.units[u].chunk].layer;
-            if (!S.lagged && k != steps) return fail("unit %lld of layer %lld at offset %lld outside the tiles-only launch", u, l, k);
-            if (!in_window(targets[l], k)) return fail("unit %lld of layer %lld at offset %lld outside its tensor's window", u, l, k);
-            umin = std::min(umin, k);
-            umax = std::max(umax, k);
-        }
-    if (S.fused)
-        for (int32_t k = 0; k < 2 * NL; ++k)
-            for (int64_t t = S.roffs[k]; t < S.roffs[k + 1]; ++t) {
-                const CleTask& tk = S.rt[t];
-                const CleRel& c = R[tk.rel];
-                bool ok = true;
-                switch (tk.kind) {
-                    case kRangeW1: ok = in_window(c.w1, k); break;
-                    case kRangeW2Contig:
-                    case kRangeW2Tile: ok = in_window(c.w2, k); break;
-                    case kRangeReset: {
-                        int32_t f, l;
-                        span(c.w2, f, l);
-                        ok = k >= rel_step[tk.rel] + 1 && k <= std::min(2 * NL - 1, NL + l);
-                        break;
-                    }
-                    default: ok = k >= rel_step[tk.rel] + 1 && k <= 2 * NL - 1;   // kRangeResetW1
-                }
-                if (!S.lagged && k != steps) ok = false;
-                if (!ok) return fail("range task %lld (kind %lld) at offset %lld outside its window", t, tk.kind, k);
-            }
-    if (S.lagged && S.stop_off >= 0) {
-        if (S.stop_off < steps || S.stop_off > 2 * NL - 1) return fail("stop rule at offset %lld of [%lld, %lld]", S.stop_off, steps, 2 * NL - 1);
-        if (umax >= 0 && S.stop_off <= umax) return fail("stop rule at offset %lld, not after the last tile offset %lld", S.stop_off, umax, 0);
-        if (umax >= 0 && umin + NL <= S.stop_off)
-            return fail("the next iteration's first tile (offset %lld + %lld) not after the stop rule at %lld", umin, NL, S.stop_off);
-    } else if (!S.lagged && S.stop_off != -1) {
-        return fail("unlagged plan with a stop-rule offset %lld", S.stop_off, 0, 0);
-    }
-    return DFQ_OK;
-}
-#endif

@@ -5,9 +5,7 @@
 
 namespace dfq {
 
-constexpr int kThreads = 256;
-constexpr int kColTileRows = 16;   // W2 rows per column tile (range and rescale tiles)
-
+// (kThreads, kColTileRows: dfq_cle_plan.h)
 __device__ __forceinline__ void cle_wave_minmax(float& lo, float& hi) {
     lo = fminf(lo, dpp_f(lo, 0xB1));
     hi = fmaxf(hi, dpp_f(hi, 0xB1));

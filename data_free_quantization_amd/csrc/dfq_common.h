@@ -8,6 +8,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "dfq_hip.h"
+#include "dfq_cle_plan.h"   // ceil_div, aten_ceil_log2, ab_env: shared with the host-only planner
 
 namespace dfq {
 
@@ -236,8 +237,6 @@ __device__ __forceinline__ float qdq_finish(float t, const QParams& p, float& q)
     return y + p.mn;
 }
 
-__host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 // ---------------------------------------------------------------------------
 // ATen's CPU fp32 summation order (at::native cascade_sum, SumKernel.cpp), which
 // the reference's torch.sum / torch.mean follow.  Characterised against torch
@@ -246,12 +245,6 @@ __host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + 
 // strided dim of >= 32768 elements, an intra-op split over columns in chunks of
 // ceil(F/threads) rounded down to multiples of 32.
 // ---------------------------------------------------------------------------
-__host__ __device__ inline int aten_ceil_log2(int64_t x) {
-    if (x <= 2) return 1;
-    int r = 0;
-    for (uint64_t v = (uint64_t)(x - 1); v; v >>= 1) ++r;
-    return r;
-}
 
 // multi_row_sum for one stream: sequential adds, flushed up a 4-level cascade.
 // Level step 16 (every size below 2^20): a compile-time step, so each level-0
@@ -525,17 +518,6 @@ void set_last_hip_error_text(const char* msg);
 // that DMA has completed.  The caller's buffer may die at return; nothing
 // synchronises the stream.
 hipError_t stage_h2d(void* dst, const void* src, size_t bytes, hipStream_t s);
-// Environment switches for A/B runs and diagnostics: read only by the diagnostics
-// library (libdfq_diag.so, built with -DDFQ_DIAGNOSTICS); the product library
-// runs its measured defaults whatever the environment says.
-inline const char* ab_env(const char* name) {
-#ifdef DFQ_DIAGNOSTICS
-    return getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
 }
 #define DFQ_HIP_CHECK(expr)                                   \
     do {                                                      \

@@ -18,8 +18,7 @@
 
 namespace dfq {
 
-constexpr int kThreads = 256;
-
+// (kThreads = 256, the block size here too: dfq_cle_plan.h through dfq_common.h)
 static int blocks_for(int64_t n, int per_thread = 1) {
     const int64_t b = ceil_div(std::max<int64_t>(n, 1), (int64_t)kThreads * per_thread);
     return (int)std::min<int64_t>(b, 256 * 8);

@@ -47,9 +47,13 @@ int dfq_probe_lds(const float* x, float* y, void* codes, float* esum, int64_t n,
  * (host code only: no device memory is touched, addresses may be stand-ins) checked
  * for every index its kernels derive from it -- task tables, range words, rollback
  * saves, metric chunks / units, the lagged placement windows and the stop rule's
- * offset (dfq_cle.hip).  info[8]: steps, nlaunch, lagged, stop_off, rescale tasks,
- * range tasks, units, chunks.  DFQ_ERR_INVALID + msg: the first violation.  Reads
- * the same diagnostics schedule switches as plan creation (DFQ_CLE_LAG, ...). */
+ * offset (the planner and this check: dfq_cle_plan.cpp, plain C++).  info[8]: steps,
+ * nlaunch, lagged, stop_off, rescale tasks, range tasks, units, chunks.  DFQ_OK +
+ * msg "digest <16 hex digits>": the structure's digest (64-bit FNV-1a over every
+ * address-free field: relations' flags, both task tables in order, chunks, units,
+ * offsets, byte totals; pinned by tests/golden/cle_structure_digests.json).
+ * DFQ_ERR_INVALID + msg: the first violation.  Reads the same diagnostics schedule
+ * switches as plan creation (DFQ_CLE_LAG, ...). */
 int dfq_diag_cle_check_structure(const dfq_cle_rel* rels, int32_t n_rel, float* const* targets,
                                  const int64_t* target_n, int32_t n_targets, int32_t ref_threads, int64_t* info,
                                  char* msg, int32_t msg_cap);
