@@ -36,6 +36,7 @@ EXPORTS = [
     "dfq_cle_plan_info", "dfq_cle_plan_set_timing", "dfq_cle_plan_stats", "dfq_cle_plan_destroy",
     "dfq_bias_absorb", "dfq_bias_absorb_ws_bytes", "dfq_bias_absorb_batch", "dfq_bc_expect", "dfq_bc_apply", "dfq_bc_propagate", "dfq_bc_chain",
     "dfq_act_moments", "dfq_act_minmax", "dfq_act_affine",
+    "dfq_pair_stats_ws_bytes", "dfq_pair_stats_batch",
 ]
 #: entry points only the diagnostics library exports (include/dfq_diag.h)
 DIAG_EXPORTS = ["dfq_probe_stream", "dfq_probe_lds", "dfq_debug_timeline", "dfq_debug_ablate",
@@ -92,9 +93,17 @@ class BcOp(C.Structure):
     ]
 
 
+class PairDesc(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("y", C.c_void_p), ("rows_out", C.c_void_p), ("total_out", C.c_void_p),
+        ("rows", C.c_int64), ("row_len", C.c_int64),
+    ]
+
+
 DFQ_BC_OP_EXPECT, DFQ_BC_OP_APPLY, DFQ_BC_OP_PROPAGATE, DFQ_BC_OP_COPY = 0, 1, 2, 3
 DFQ_BC_APPLY_VEC_SCRATCH = 1
 DFQ_BN_FOLD_ZERO_BIAS = 1
+DFQ_PAIR_PIECE_ELEMS = 8192
 
 _LIB: Optional[C.CDLL] = None
 
@@ -171,6 +180,8 @@ def load(path: Optional[os.PathLike] = None) -> C.CDLL:
         "dfq_act_moments": ([P, P, I64, I32, I32, F32, I32, P, P, P], C.c_int),
         "dfq_act_minmax": ([P, P, I64, I32, F32, F32, P, P], C.c_int),
         "dfq_act_affine": ([P, P, P, I64, I64, I64, I64, P, P], C.c_int),
+        "dfq_pair_stats_ws_bytes": ([C.POINTER(PairDesc), I32], C.c_int64),
+        "dfq_pair_stats_batch": ([C.POINTER(PairDesc), I32, P, I64, P], C.c_int),
     }
     diag = {
         "dfq_probe_stream": ([P, P, P, P, I64, I32, P], C.c_int),

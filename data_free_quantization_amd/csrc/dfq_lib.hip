@@ -122,12 +122,14 @@ constexpr size_t kStagePreloadSlots = 8;
 hipError_t preload_sweep();
 hipError_t preload_transform();
 hipError_t preload_cle();
+hipError_t preload_stats();
 }  // namespace dfq
 
 extern "C" int dfq_preload(void) {
     DFQ_HIP_CHECK(dfq::preload_sweep());
     DFQ_HIP_CHECK(dfq::preload_transform());
     DFQ_HIP_CHECK(dfq::preload_cle());
+    DFQ_HIP_CHECK(dfq::preload_stats());
     DFQ_HIP_CHECK(dfq::stage_preload(dfq::kStagePreloadSlots));
     return DFQ_OK;
 }

@@ -15,6 +15,9 @@ Same flags and stage order; the transforms run on the GPU.  Additive flags:
   --world_size N       shard quantize_targ_layer's layer list over N ranks (one
                        process per GPU under torchrun, RCCL all-gather of the
                        results; distributed.py); rank 0 evaluates / logs / exports
+  --report PATH        write the data-free quality report (quality.py: per-layer and
+                       per-channel SQNR of the quantized weights against their values
+                       before quantization, as JSON); needs --quantize
 
 Example (README.md:137 of the reference):
   python -m data_free_quantization_amd.main_dfq --task cls --relu --equalize --absorption \
@@ -75,7 +78,12 @@ def get_argument(argv=None):
                    help="write the integer weights (codes, scale, zero, bias) to this safetensors file")
     p.add_argument("--world_size", type=int, default=1,
                    help="ranks sharing quantize_targ_layer's layer list (launch with torchrun --nproc-per-node N)")
-    return p.parse_args(argv)
+    p.add_argument("--report", default=None,
+                   help="write the weight quantization quality report (per-channel SQNR, JSON) to this file")
+    args = p.parse_args(argv)
+    if args.report and not args.quantize:
+        p.error("--report needs --quantize")
+    return args
 
 
 def _model_name(args):
@@ -192,6 +200,9 @@ def main(argv=None):
         fold_ranges = {} if (args.granularity == "tensor" and not sharded) else None
         model = merge_batchnorm(model, graph, bottoms, targ_layer, ranges=fold_ranges)
         fused_clip = [-15, 15] if (args.clip_weight and args.bc_mode == "fused") else None
+        if args.report:   # the weights the quantizer is about to see (every rank: same stage order)
+            from . import quality
+            snap = quality.snapshot(graph, targ_layer)
         graph = quantize_targ_layer(graph, args.bits_weight, args.bits_bias, targ_layer,
                                     granularity=args.granularity, symmetric=args.symmetric, clip=fused_clip,
                                     state=state, shard=sharded, weight_ranges=fold_ranges)
@@ -213,6 +224,20 @@ def main(argv=None):
         export.save(args.export, graph, state, bits=args.bits_weight, granularity=args.granularity,
                     symmetric=args.symmetric, clip=clip)
         print(f"Exported {len(state)} quantized layers to {args.export}")
+    if args.report and rank == 0:   # sharded runs: every rank holds every result after the gather
+        import json
+        rep = quality.weight_report(graph, snap, config={
+            "model": name, "bits_weight": args.bits_weight, "granularity": args.granularity,
+            "symmetric": args.symmetric, "equalize": args.equalize, "absorption": args.absorption,
+            "clip": args.clip_weight, "clip_range": [-15.0, 15.0], "bc_mode": args.bc_mode,
+            "world_size": args.world_size})
+        with open(args.report, "w") as f:
+            json.dump(rep, f, indent=1, allow_nan=False)
+        m = rep["model"]
+        worst = next((e for e in rep["layers"] if e["key"] == m["worst_layer"]), None)
+        print("Quality report: model SQNR {} dB, worst layer {} ({} dB) -> {}".format(
+            "n/a" if m["sqnr_db"] is None else f"{m['sqnr_db']:.2f}", m["worst_layer"],
+            "n/a" if worst is None else f"{worst['sqnr_db']:.2f}", args.report))
 
     # main_dfq.py:237-240: inference in eval mode -- also the observers set_layer_bits
     # created (new modules start in training mode)

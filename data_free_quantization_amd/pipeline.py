@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import Cross_layer_equal as cle
+from . import quality
 from .bias_absorption import bias_absorption
 from .bias_correction import bias_correction
 from .clip_weight import clip_weight
@@ -33,9 +34,12 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
             absorption: bool = True, quantize: bool = True, clip: bool = True, correction: bool = True,
             bits_weight: int = 8, bits_activation: int = 8, bits_bias: int = 8, granularity: str = "tensor",
             symmetric: bool = False, bc_mode: str = "literal", clip_range=(-15, 15),
-            stage_hook: Optional[Callable[[str], None]] = None, timings: Optional[Dict] = None):
+            stage_hook: Optional[Callable[[str], None]] = None, timings: Optional[Dict] = None,
+            report: Optional[dict] = None):
     """Run the DFQ stages on ``model`` (already on the GPU) in place; returns the
-    equalization relations."""
+    equalization relations.  ``report``: a dict to fill with the quality report
+    (quality.weight_report) of the quantized weights against their values after
+    the second BN fold; needs ``quantize``.  None: no clone, no extra launch."""
     assert relu or relu == equalize, "must replace relu6 to relu while equalization"
     assert equalize or absorption == equalize, "must use absorption with equalize"
     t = timings if timings is not None else {}
@@ -63,16 +67,24 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
     if absorption:
         stage("absorb", bias_absorption, graph, res, bottoms, N=3)
     state = {} if (correction and bc_mode == "fused") else None
+    snap = None
     if quantize:
         set_layer_bits(graph, bits_weight, bits_activation, bits_bias, targ)
         # the second fold hands the folded weights' ranges to the quantize sweep
         fold_ranges = {} if granularity == "tensor" else None
         stage("bn2", merge_batchnorm, model, graph, bottoms, targ, ranges=fold_ranges)
         fused_clip = tuple(clip_range) if (clip and bc_mode == "fused") else None
+        if report is not None:
+            snap = quality.snapshot(graph, targ)
         stage("quant", quantize_targ_layer, graph, bits_weight, bits_bias, targ, granularity=granularity,
               symmetric=symmetric, clip=fused_clip, state=state, weight_ranges=fold_ranges)
     if clip and not (quantize and bc_mode == "fused"):
         stage("clip", clip_weight, graph, range_clip=list(clip_range), targ_type=targ)
+    if snap is not None:   # the weights are final from here (bias correction rewrites biases only)
+        report.update(quality.weight_report(graph, snap, config={
+            "bits_weight": bits_weight, "granularity": granularity, "symmetric": bool(symmetric),
+            "equalize": bool(equalize), "absorption": bool(absorption), "clip": bool(clip),
+            "clip_range": [float(c) for c in clip_range], "bc_mode": bc_mode}))
     if correction:
         err = None
         if bc_mode == "fused":

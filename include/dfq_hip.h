@@ -332,6 +332,42 @@ int dfq_cle_plan_set_timing(dfq_cle_plan* plan, int32_t on);
 int dfq_cle_plan_stats(const dfq_cle_plan* plan, int64_t* bytes, double* loop_ms, int32_t* launched);
 int dfq_cle_plan_destroy(dfq_cle_plan* plan);
 
+/* ---- pair statistics: per-channel signal, noise, worst error and range -----
+ * (no working reference counterpart: the reference's quantize_error.py raises).
+ * Many (reference x, compared y) fp32 tensor pairs in one call, each viewed as
+ * [rows, row_len] like the sweep.  With e_i = fl32(y_i - x_i) (the fp32 difference
+ * of the sweep's esum), row r's record is 4 doubles:
+ *   [0] signal  = sum_i (double)x_i * (double)x_i
+ *   [1] noise   = sum_i (double)e_i * (double)e_i
+ *   [2] max_err = max_i |e_i|   (an fp32 value widened)
+ *   [3] max_abs = max_i |x_i|   (an fp32 value widened)
+ * and the pair's totals are {sum_r signal, sum_r noise, max_r max_err, max_r max_abs}.
+ * Sums are accumulated in fp64 (every term is an exact double).  A pair's result
+ * is the same bits from run to run, whatever the grid, the rest of the list or
+ * the pair's place in it: the partition depends on the pair's shape only, partial
+ * sums are combined in a fixed index order, and no floating-point atomic is used
+ * (which elements a lane adds depends on x's address modulo 16).  Non-finite
+ * inputs are outside the contract, as for weights. */
+enum { DFQ_PAIR_PIECE_ELEMS = 8192 };   /* a row longer than this is cut into pieces of this many elements */
+typedef struct dfq_pair_desc {
+    const float* x;         /* reference, 4-B aligned */
+    const float* y;         /* compared, same shape, 4-B aligned */
+    double*      rows_out;  /* [rows][4] or NULL */
+    double*      total_out; /* [4] or NULL (not both NULL) */
+    int64_t      rows;      /* >= 1 */
+    int64_t      row_len;   /* >= 1 */
+} dfq_pair_desc;
+/* Device workspace bytes for dfq_pair_stats_batch (-1: bad arguments). */
+int64_t dfq_pair_stats_ws_bytes(const dfq_pair_desc* descs, int32_t n);
+/* Two launches, asynchronous on `stream`, no host wait (the tables go up through
+ * the library's pinned staging ring).  ws: >= dfq_pair_stats_ws_bytes bytes,
+ * 256-B aligned, stream-ordered with `stream` (e.g. the framework's caching
+ * allocator); DFQ_ERR_WORKSPACE if it is NULL or too small, DFQ_ERR_INVALID if it
+ * is misaligned.  x and y are only
+ * read; where their addresses differ modulo 16 the pair is read with 4-B loads.
+ * n == 0: DFQ_OK, nothing launched. */
+int dfq_pair_stats_batch(const dfq_pair_desc* descs, int32_t n, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- high-bias absorption (bias_absorption.py:147-197) ------------------
  * c = max(bn_b - N*bn_w, 0) (bn_* = the BN's fake_weight / fake_bias);
  * b2[o] += sum_i (sum_k W2[o,i,k]) * c[g*i2 + i];  b1 -= c;  bn_b -= c.
