@@ -37,6 +37,7 @@ EXPORTS = [
     "dfq_bias_absorb", "dfq_bias_absorb_ws_bytes", "dfq_bias_absorb_batch", "dfq_bc_expect", "dfq_bc_apply", "dfq_bc_propagate", "dfq_bc_chain",
     "dfq_act_moments", "dfq_act_minmax", "dfq_act_affine",
     "dfq_pair_stats_ws_bytes", "dfq_pair_stats_batch",
+    "dfq_clip_search_ws_bytes", "dfq_clip_search_batch",
 ]
 #: entry points only the diagnostics library exports (include/dfq_diag.h)
 DIAG_EXPORTS = ["dfq_probe_stream", "dfq_probe_lds", "dfq_debug_timeline", "dfq_debug_ablate",
@@ -100,10 +101,19 @@ class PairDesc(C.Structure):
     ]
 
 
+class ClipSearchDesc(C.Structure):
+    _fields_ = [
+        ("w", C.c_void_p), ("rows", C.c_int64), ("row_len", C.c_int64), ("bits", C.c_int32), ("mode", C.c_int32),
+        ("candidates", C.c_int32), ("flags", C.c_int32), ("min_frac", C.c_float), ("reserved", C.c_int32),
+        ("choice", C.c_void_p), ("range", C.c_void_p), ("noise", C.c_void_p), ("range_enc", C.c_void_p),
+    ]
+
+
 DFQ_BC_OP_EXPECT, DFQ_BC_OP_APPLY, DFQ_BC_OP_PROPAGATE, DFQ_BC_OP_COPY = 0, 1, 2, 3
 DFQ_BC_APPLY_VEC_SCRATCH = 1
 DFQ_BN_FOLD_ZERO_BIAS = 1
 DFQ_PAIR_PIECE_ELEMS = 8192
+DFQ_CLIP_PIECE_ELEMS, DFQ_CLIP_MAX_CANDIDATES, DFQ_CLIP_SEARCH_DRY = 4096, 64, 1
 
 _LIB: Optional[C.CDLL] = None
 
@@ -182,6 +192,8 @@ def load(path: Optional[os.PathLike] = None) -> C.CDLL:
         "dfq_act_affine": ([P, P, P, I64, I64, I64, I64, P, P], C.c_int),
         "dfq_pair_stats_ws_bytes": ([C.POINTER(PairDesc), I32], C.c_int64),
         "dfq_pair_stats_batch": ([C.POINTER(PairDesc), I32, P, I64, P], C.c_int),
+        "dfq_clip_search_ws_bytes": ([C.POINTER(ClipSearchDesc), I32], C.c_int64),
+        "dfq_clip_search_batch": ([C.POINTER(ClipSearchDesc), I32, P, I64, P], C.c_int),
     }
     diag = {
         "dfq_probe_stream": ([P, P, P, P, I64, I32, P], C.c_int),

@@ -123,6 +123,7 @@ hipError_t preload_sweep();
 hipError_t preload_transform();
 hipError_t preload_cle();
 hipError_t preload_stats();
+hipError_t preload_clip();
 }  // namespace dfq
 
 extern "C" int dfq_preload(void) {
@@ -130,6 +131,7 @@ extern "C" int dfq_preload(void) {
     DFQ_HIP_CHECK(dfq::preload_transform());
     DFQ_HIP_CHECK(dfq::preload_cle());
     DFQ_HIP_CHECK(dfq::preload_stats());
+    DFQ_HIP_CHECK(dfq::preload_clip());
     DFQ_HIP_CHECK(dfq::stage_preload(dfq::kStagePreloadSlots));
     return DFQ_OK;
 }

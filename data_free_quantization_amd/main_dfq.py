@@ -18,6 +18,13 @@ Same flags and stage order; the transforms run on the GPU.  Additive flags:
   --report PATH        write the data-free quality report (quality.py: per-layer and
                        per-channel SQNR of the quantized weights against their values
                        before quantization, as JSON); needs --quantize
+  --clip_search        before quantizing, clamp every weight (per channel or per tensor,
+                       as --granularity) to the one of --clip_candidates K ranges between
+                       its min-max range and --clip_min_frac of it that minimizes its own
+                       quantization noise (clip_weight.search_clip); needs --quantize.
+                       The defaults (16, 0.5) are interface choices: no dataset ships
+                       here to tune them on.  --report then counts, per layer, the units
+                       that chose a narrower range and those at the narrowest candidate
 
 Example (README.md:137 of the reference):
   python -m data_free_quantization_amd.main_dfq --task cls --relu --equalize --absorption \
@@ -36,7 +43,7 @@ import torch.nn as nn
 from . import _lib, zoo
 from .bias_absorption import bias_absorption
 from .bias_correction import bias_correction
-from .clip_weight import clip_weight
+from .clip_weight import clip_weight, search_clip
 from .Cross_layer_equal import cross_layer_equalization, wait as cle_wait
 from .utils.layer_transform import (esum_source, merge_batchnorm, quantize_targ_layer, replace_op, restore_op,
                                     set_quant_minmax, switch_layers)
@@ -80,9 +87,21 @@ def get_argument(argv=None):
                    help="ranks sharing quantize_targ_layer's layer list (launch with torchrun --nproc-per-node N)")
     p.add_argument("--report", default=None,
                    help="write the weight quantization quality report (per-channel SQNR, JSON) to this file")
+    p.add_argument("--clip_search", action="store_true",
+                   help="clamp each weight to the candidate range with the least quantization noise before quantizing")
+    p.add_argument("--clip_candidates", type=int, default=16, help="candidate ranges per unit (1..64)")
+    p.add_argument("--clip_min_frac", type=float, default=0.5,
+                   help="the narrowest candidate as a share of the min-max range, in [0, 1]")
     args = p.parse_args(argv)
     if args.report and not args.quantize:
         p.error("--report needs --quantize")
+    if args.clip_search and not args.quantize:
+        p.error("--clip_search needs --quantize")
+    if args.clip_search and args.world_size > 1:
+        p.error("--clip_search is not sharded: run it with --world_size 1")
+    if args.clip_search and not (1 <= args.clip_candidates <= _lib.DFQ_CLIP_MAX_CANDIDATES and
+                                 0.0 <= args.clip_min_frac <= 1.0):
+        p.error("--clip_candidates takes 1..%d and --clip_min_frac a value in [0, 1]" % _lib.DFQ_CLIP_MAX_CANDIDATES)
     return args
 
 
@@ -203,6 +222,11 @@ def main(argv=None):
         if args.report:   # the weights the quantizer is about to see (every rank: same stage order)
             from . import quality
             snap = quality.snapshot(graph, targ_layer)
+        searched = None
+        if args.clip_search:   # rewrites fold_ranges with the clamped weights' ranges (one-pass sweep)
+            searched = search_clip(graph, args.bits_weight, granularity=args.granularity, symmetric=args.symmetric,
+                                   candidates=args.clip_candidates, min_frac=args.clip_min_frac,
+                                   targ_type=targ_layer, weight_ranges=fold_ranges)
         graph = quantize_targ_layer(graph, args.bits_weight, args.bits_bias, targ_layer,
                                     granularity=args.granularity, symmetric=args.symmetric, clip=fused_clip,
                                     state=state, shard=sharded, weight_ranges=fold_ranges)
@@ -230,7 +254,9 @@ def main(argv=None):
             "model": name, "bits_weight": args.bits_weight, "granularity": args.granularity,
             "symmetric": args.symmetric, "equalize": args.equalize, "absorption": args.absorption,
             "clip": args.clip_weight, "clip_range": [-15.0, 15.0], "bc_mode": args.bc_mode,
-            "world_size": args.world_size})
+            "world_size": args.world_size,
+            **({"clip_search": True, "clip_candidates": args.clip_candidates, "clip_min_frac": args.clip_min_frac}
+               if args.clip_search else {})}, clip_search=searched)
         with open(args.report, "w") as f:
             json.dump(rep, f, indent=1, allow_nan=False)
         m = rep["model"]

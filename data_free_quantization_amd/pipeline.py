@@ -2,8 +2,8 @@
 (main_dfq.py:188-231), on the GPU:
 
   merge_batchnorm -> create_relation -> cross_layer_equalization ->
-  bias_absorption -> set_layer_bits -> merge_batchnorm -> quantize_targ_layer ->
-  clip_weight -> bias_correction
+  bias_absorption -> set_layer_bits -> merge_batchnorm -> [search_clip] ->
+  quantize_targ_layer -> clip_weight -> bias_correction
 
 ``bc_mode``:
   * "literal"   -- exactly the reference: BC walks with the graph's keys (a no-op
@@ -24,7 +24,7 @@ from . import Cross_layer_equal as cle
 from . import quality
 from .bias_absorption import bias_absorption
 from .bias_correction import bias_correction
-from .clip_weight import clip_weight
+from .clip_weight import clip_weight, search_clip
 from .utils.layer_transform import esum_source, merge_batchnorm, quantize_targ_layer
 from .utils.quantize import set_layer_bits
 from .utils.relation import create_relation
@@ -35,11 +35,17 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
             bits_weight: int = 8, bits_activation: int = 8, bits_bias: int = 8, granularity: str = "tensor",
             symmetric: bool = False, bc_mode: str = "literal", clip_range=(-15, 15),
             stage_hook: Optional[Callable[[str], None]] = None, timings: Optional[Dict] = None,
-            report: Optional[dict] = None):
+            report: Optional[dict] = None, clip_search: Optional[dict] = None):
     """Run the DFQ stages on ``model`` (already on the GPU) in place; returns the
     equalization relations.  ``report``: a dict to fill with the quality report
     (quality.weight_report) of the quantized weights against their values after
-    the second BN fold; needs ``quantize``.  None: no clone, no extra launch."""
+    the second BN fold; needs ``quantize``.  None: no clone, no extra launch.
+    ``clip_search``: None, or {"candidates": K, "min_frac": f} (either may be left
+    out: 16, 0.5) to clamp every weight, before it is quantized, to the range that
+    minimizes its own quantization noise (clip_weight.search_clip; stage
+    "clipsearch", after the report's snapshot, so the report measures the noise
+    against the unclamped weights); needs ``quantize``.  Bias correction sees the
+    clamped weight as its input."""
     assert relu or relu == equalize, "must replace relu6 to relu while equalization"
     assert equalize or absorption == equalize, "must use absorption with equalize"
     t = timings if timings is not None else {}
@@ -67,7 +73,10 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
     if absorption:
         stage("absorb", bias_absorption, graph, res, bottoms, N=3)
     state = {} if (correction and bc_mode == "fused") else None
-    snap = None
+    snap = searched = None
+    cs_cfg = {}
+    if clip_search is not None and not quantize:
+        raise ValueError("clip_search needs quantize")
     if quantize:
         set_layer_bits(graph, bits_weight, bits_activation, bits_bias, targ)
         # the second fold hands the folded weights' ranges to the quantize sweep
@@ -76,6 +85,13 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
         fused_clip = tuple(clip_range) if (clip and bc_mode == "fused") else None
         if report is not None:
             snap = quality.snapshot(graph, targ)
+        if clip_search is not None:
+            cs_cfg = {"clip_search": True, "clip_candidates": int(clip_search.get("candidates", 16)),
+                      "clip_min_frac": float(clip_search.get("min_frac", 0.5))}
+            # rewrites fold_ranges with the clamped weights' ranges: the sweep stays one pass
+            searched = stage("clipsearch", search_clip, graph, bits_weight, granularity=granularity,
+                             symmetric=symmetric, candidates=cs_cfg["clip_candidates"],
+                             min_frac=cs_cfg["clip_min_frac"], targ_type=targ, weight_ranges=fold_ranges)
         stage("quant", quantize_targ_layer, graph, bits_weight, bits_bias, targ, granularity=granularity,
               symmetric=symmetric, clip=fused_clip, state=state, weight_ranges=fold_ranges)
     if clip and not (quantize and bc_mode == "fused"):
@@ -84,7 +100,7 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
         report.update(quality.weight_report(graph, snap, config={
             "bits_weight": bits_weight, "granularity": granularity, "symmetric": bool(symmetric),
             "equalize": bool(equalize), "absorption": bool(absorption), "clip": bool(clip),
-            "clip_range": [float(c) for c in clip_range], "bc_mode": bc_mode}))
+            "clip_range": [float(c) for c in clip_range], "bc_mode": bc_mode, **cs_cfg}, clip_search=searched))
     if correction:
         err = None
         if bc_mode == "fused":

@@ -178,10 +178,17 @@ def build_report(entries, config: dict) -> dict:
     return {"format": FORMAT, "config": dict(config), "layers": layers, "model": model_entry(layers)}
 
 
-def weight_report(graph, snap: Dict, *, config: dict) -> dict:
+def weight_report(graph, snap: Dict, *, config: dict, clip_search: Optional[Dict] = None) -> dict:
     """The report of ``graph``'s target weights against ``snap`` (``snapshot``'s
     clones, taken before the quantization): one pair_stats call over
-    (snap[k], graph[k].weight) in graph order, one device-to-host copy."""
+    (snap[k], graph[k].weight) in graph order, one device-to-host copy.
+
+    ``clip_search``: what ``clip_weight.search_clip`` returned for a search run
+    between the snapshot and the quantization.  Each layer entry then also counts
+    its units (``clip_units``: channels, or 1 for the tensor), those that chose a
+    narrower range than min-max (``clip_narrowed``) and those that chose the narrowest candidate
+    (``clip_at_edge``: many of them say min_frac should be lower); the caller
+    records the search's settings in ``config``."""
     keys = [k for k in graph if k in snap]
     call = PairStatsCall([(snap[k], graph[k].weight.detach()) for k in keys])
     call.run()
@@ -194,4 +201,18 @@ def weight_report(graph, snap: Dict, *, config: dict) -> dict:
         entries.append((k, type(graph[k]).__name__, tuple(w.shape), host[4 * row0:4 * (row0 + rows)].reshape(rows, 4),
                         host[4 * (n_rows + i):4 * (n_rows + i + 1)]))
         row0 += rows
-    return build_report(entries, config)
+    rep = build_report(entries, config)
+    if clip_search is not None:
+        last = int(config["clip_candidates"]) - 1
+        found = [k for k in keys if k in clip_search]
+        flat = torch.cat([clip_search[k]["choice"].reshape(-1) for k in found]).cpu().numpy() if found else None
+        at = 0
+        for e, k in zip(rep["layers"], keys):
+            if k not in clip_search:
+                continue
+            c = flat[at:at + clip_search[k]["choice"].numel()]
+            at += c.size
+            e["clip_units"] = int(c.size)
+            e["clip_narrowed"] = int((c > 0).sum())
+            e["clip_at_edge"] = int(((c > 0) & (c == last)).sum())
+    return rep

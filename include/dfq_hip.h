@@ -368,6 +368,59 @@ int64_t dfq_pair_stats_ws_bytes(const dfq_pair_desc* descs, int32_t n);
  * n == 0: DFQ_OK, nothing launched. */
 int dfq_pair_stats_batch(const dfq_pair_desc* descs, int32_t n, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- clip-range search: the clamp that minimizes a weight's own quantization
+ *      noise (no reference counterpart: the reference's clip_weight.py clamps to
+ *      a fixed [-15, 15]) -----------------------------------------------------
+ * A unit is one row of the [rows, row_len] view in the CHANNEL modes and the whole
+ * tensor in the TENSOR modes.  For a unit with fp32 data range (mn, mx), candidate
+ * k of K = `candidates` is
+ *   a_k  = (float)(1.0 - k * (1.0 - (double)min_frac) / (K - 1))     (a_0 = 1; K = 1: a_0 only)
+ *   lo_k = a_k * mn,  hi_k = a_k * mx                                 (fp32 multiplies)
+ *   c_i  = min(max(x_i, lo_k), hi_k)
+ *   y_i  = the sweep's quantize-dequantize of c_i on c's data range
+ *          (min(max(mn, lo_k), hi_k), min(max(mx, lo_k), hi_k)) at `bits` in `mode`
+ *   noise_k = sum_i (double)e_i * (double)e_i,  e_i = fl32(y_i - x_i) -- against the UNCLAMPED x_i
+ * and the choice is the smallest noise_k, ties to the smallest k (so a constant
+ * unit chooses 0, and the chosen noise never exceeds the min-max range's).  Unless
+ * DFQ_CLIP_SEARCH_DRY is set, w then holds c of the chosen k, and a sweep of w in
+ * the same mode and bits reproduces y bit for bit.  Every term of a sum is an
+ * exact double; the sums round.  A unit's results are the same bits from run to
+ * run, whatever the rest of the list or the unit's place in it (the partition
+ * depends on the shape alone, partials combine in index order, no floating-point
+ * atomic).  Non-finite weights are outside the contract. */
+enum { DFQ_CLIP_PIECE_ELEMS = 4096 };  /* a unit longer than this is cut into pieces of this many elements */
+enum { DFQ_CLIP_MAX_CANDIDATES = 64 };
+enum { DFQ_CLIP_SEARCH_DRY = 1 };      /* search and report; leave w untouched */
+typedef struct dfq_clip_search_desc {
+    float*    w;          /* in place, 4-B aligned */
+    int64_t   rows;       /* >= 1 */
+    int64_t   row_len;    /* >= 1 */
+    int32_t   bits;       /* 2..16 */
+    int32_t   mode;       /* DFQ_TENSOR_ASYM ... DFQ_CHANNEL_SYM */
+    int32_t   candidates; /* K: 1..DFQ_CLIP_MAX_CANDIDATES */
+    int32_t   flags;      /* DFQ_CLIP_SEARCH_DRY or 0 */
+    float     min_frac;   /* the narrowest candidate's share of the range, in [0, 1] */
+    int32_t   reserved;
+    /* outputs, each may be NULL; units = rows (CHANNEL modes) or 1 (TENSOR modes) */
+    int32_t*  choice;     /* [units] the chosen k */
+    float*    range;      /* [units][2] the chosen (lo_k, hi_k) */
+    double*   noise;      /* [units][2] noise_0 and the chosen noise_k */
+    uint32_t* range_enc;  /* TENSOR modes: 2 words, {~enc(min), enc(max)} of the tensor as the call leaves
+                           * it (clamped, or untouched under DFQ_CLIP_SEARCH_DRY), dfq_range's encoding:
+                           * a later sweep with DFQ_DEVICE_RANGE stays one pass.  CHANNEL modes: ignored */
+} dfq_clip_search_desc;
+/* Device workspace bytes for dfq_clip_search_batch (-1: bad arguments). */
+int64_t dfq_clip_search_ws_bytes(const dfq_clip_search_desc* descs, int32_t n);
+/* Asynchronous on `stream`, no host wait (the tables go up through the library's
+ * pinned staging ring): one launch when no unit is longer than a piece, else a
+ * range, a piece, a finish and a clamp launch (launches without work are skipped).
+ * ws as for dfq_pair_stats_batch: >= dfq_clip_search_ws_bytes bytes, 256-B aligned,
+ * stream-ordered with `stream`; DFQ_ERR_WORKSPACE if it is NULL or too small,
+ * DFQ_ERR_INVALID if it is misaligned or a descriptor is bad (bits, candidates,
+ * min_frac outside [0, 1] or NaN, mode, unknown flags, sizes, alignment).  Each
+ * weight at most once per call.  n == 0: DFQ_OK, nothing launched. */
+int dfq_clip_search_batch(const dfq_clip_search_desc* descs, int32_t n, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- high-bias absorption (bias_absorption.py:147-197) ------------------
  * c = max(bn_b - N*bn_w, 0) (bn_* = the BN's fake_weight / fake_bias);
  * b2[o] += sum_i (sum_k W2[o,i,k]) * c[g*i2 + i];  b1 -= c;  bn_b -= c.
