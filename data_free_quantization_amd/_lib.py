@@ -38,6 +38,7 @@ EXPORTS = [
     "dfq_act_moments", "dfq_act_minmax", "dfq_act_affine",
     "dfq_pair_stats_ws_bytes", "dfq_pair_stats_batch",
     "dfq_clip_search_ws_bytes", "dfq_clip_search_batch",
+    "dfq_mx_quantize_ws_bytes", "dfq_mx_quantize_batch",
 ]
 #: entry points only the diagnostics library exports (include/dfq_diag.h)
 DIAG_EXPORTS = ["dfq_probe_stream", "dfq_probe_lds", "dfq_debug_timeline", "dfq_debug_ablate",
@@ -109,11 +110,22 @@ class ClipSearchDesc(C.Structure):
     ]
 
 
+class MxDesc(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("dst", C.c_void_p), ("codes", C.c_void_p), ("scales", C.c_void_p), ("esum", C.c_void_p),
+        ("rows", C.c_int64), ("row_len", C.c_int64), ("khw", C.c_int32), ("format", C.c_int32), ("flags", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 DFQ_BC_OP_EXPECT, DFQ_BC_OP_APPLY, DFQ_BC_OP_PROPAGATE, DFQ_BC_OP_COPY = 0, 1, 2, 3
 DFQ_BC_APPLY_VEC_SCRATCH = 1
 DFQ_BN_FOLD_ZERO_BIAS = 1
 DFQ_PAIR_PIECE_ELEMS = 8192
 DFQ_CLIP_PIECE_ELEMS, DFQ_CLIP_MAX_CANDIDATES, DFQ_CLIP_SEARCH_DRY = 4096, 64, 1
+DFQ_MX_BLOCK = 32
+DFQ_MX_FP4_E2M1, DFQ_MX_FP8_E4M3 = 0, 1
+DFQ_MX_TASK_ELEMS, DFQ_MX_ESUM_TASK_ELEMS = 4096, 2048
 
 _LIB: Optional[C.CDLL] = None
 
@@ -194,6 +206,8 @@ def load(path: Optional[os.PathLike] = None) -> C.CDLL:
         "dfq_pair_stats_batch": ([C.POINTER(PairDesc), I32, P, I64, P], C.c_int),
         "dfq_clip_search_ws_bytes": ([C.POINTER(ClipSearchDesc), I32], C.c_int64),
         "dfq_clip_search_batch": ([C.POINTER(ClipSearchDesc), I32, P, I64, P], C.c_int),
+        "dfq_mx_quantize_ws_bytes": ([C.POINTER(MxDesc), I32], C.c_int64),
+        "dfq_mx_quantize_batch": ([C.POINTER(MxDesc), I32, P, I64, P], C.c_int),
     }
     diag = {
         "dfq_probe_stream": ([P, P, P, P, I64, I32, P], C.c_int),

@@ -124,6 +124,7 @@ hipError_t preload_transform();
 hipError_t preload_cle();
 hipError_t preload_stats();
 hipError_t preload_clip();
+hipError_t preload_mx();
 }  // namespace dfq
 
 extern "C" int dfq_preload(void) {
@@ -132,6 +133,7 @@ extern "C" int dfq_preload(void) {
     DFQ_HIP_CHECK(dfq::preload_cle());
     DFQ_HIP_CHECK(dfq::preload_stats());
     DFQ_HIP_CHECK(dfq::preload_clip());
+    DFQ_HIP_CHECK(dfq::preload_mx());
     DFQ_HIP_CHECK(dfq::stage_preload(dfq::kStagePreloadSlots));
     return DFQ_OK;
 }

@@ -1,0 +1,294 @@
+// dfq_mx_quantize_batch: OCP Microscaling (MX) block-scaled quantization of every
+// tensor of a list in one launch and one HBM pass (include/dfq_hip.h).  One wave per
+// task of the planner's table (dfq_mx_plan.h).
+//
+// A task's padded elements (its rows, each padded to whole 32-element MX blocks) are
+// numbered v = 0, 1, ...; one wave round takes 256 of them, four consecutive ones per
+// lane, so eight neighbouring lanes hold one MX block: the block's amax is a maximum
+// over those eight lanes (DPP, on the magnitudes' bit patterns: integer compares,
+// no NaN rule, no canonicalisation), each lane converts its four elements and stores
+// 16 B of dst, 2 B of packed FP4 or 4 B of FP8, and the block's first lane its scale
+// byte -- all of them consecutive across the wave.  Codes and scales are addressed by
+// v alone ([rows, nb, 16 | 32] and [rows, nb] are the padded numbering), so the
+// padding of a partial block is written as +0 codes by the lanes that hold it.
+// Rows that do not start 16-B aligned take the same walk with 4-B accesses.
+// The conversion is plain integer / fp32 arithmetic (mx_encode): exact power-of-two
+// scalings, one round-to-nearest-even (v_rndne_f32) and a saturating integer min.
+// (gfx950's v_cvt_scalef32_pk_fp8_f32 gives the E4M3 NaN code 0x7F where the contract
+// saturates to 448, and a build on the scaled converts was no faster: DESIGN.md 3.7.)
+// Error sums: khw == 1 stores fl32(y - x) as it goes; khw > 1 keeps the task's
+// errors in the wave's LDS copy and one lane adds each khw group in ATen's order
+// (aten_inner_sum, the sweep's helper).  No atomic, nothing handed between waves.
+#include "dfq_common.h"
+#include "dfq_mx_plan.h"
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+namespace dfq {
+namespace {
+
+constexpr int kMxWaves = kThreads / kWave;
+constexpr int kMxBatch = 4;   // rounds whose loads are issued together (dst may alias src: the
+                              // compiler cannot move a round's loads above the previous round's stores)
+
+template <int FMT>
+struct MxFmt;
+template <>
+struct MxFmt<DFQ_MX_FP4_E2M1> {
+    static constexpr int mbits = 1, emin = 0, emax = 2, max_code = 0x7, sign = 0x8;
+};
+template <>
+struct MxFmt<DFQ_MX_FP8_E4M3> {
+    static constexpr int mbits = 3, emin = -6, emax = 8, max_code = 0x7E, sign = 0x80;   // 0x7F is NaN
+};
+
+__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }   // -127 <= e <= 127; -127: +0
+
+// The shared exponent X of a block whose largest magnitude has the bits `amax_bits`.
+template <int FMT>
+__device__ __forceinline__ int mx_exponent(uint32_t amax_bits) {
+    if (amax_bits == 0) return -127;
+    const int x = (int)(amax_bits >> 23) - 127 - MxFmt<FMT>::emax;   // floor(log2 amax) is the fp32 exponent
+    return x < -127 ? -127 : x;                                      // <= 127 - emax
+}
+
+// One element: its code and y = +-q * 2^X.  inv = 2^-X, up = 2^X.
+//   v = |x| * 2^-X in [0, 2^(emax+1));  e = max(exponent(v), emin);  n = rne(v * 2^(mbits-e)), an
+//   integer in [0, 2^(mbits+1)];  magnitude code = n + ((e - emin) << mbits): n < 2^mbits only in the
+//   subnormal binade (exponent field 0), n == 2^(mbits+1) carries into the next binade's first code,
+//   and an even n is an even code, so round-half-even on n is ties-to-even-code.  The codes ascend
+//   with the magnitudes, so the integer min with the largest finite code saturates.
+template <int FMT>
+__device__ __forceinline__ uint32_t mx_encode(float x, float inv, float up, float& y) {
+    using F = MxFmt<FMT>;
+    const uint32_t xb = __float_as_uint(x);
+    const float v = __uint_as_float(xb & 0x7fffffffu) * inv;
+    int e = (int)(__float_as_uint(v) >> 23) - 127;
+    e = e < F::emin ? F::emin : e;
+    const float n = rintf(v * pow2f(F::mbits - e));
+    uint32_t code = (uint32_t)(int)n + ((uint32_t)(e - F::emin) << F::mbits);
+    float q = n * pow2f(e - F::mbits);
+    if (code > (uint32_t)F::max_code) {
+        code = F::max_code;
+        q = FMT == DFQ_MX_FP4_E2M1 ? 6.0f : 448.0f;
+    }
+    const uint32_t sb = xb & 0x80000000u;
+    y = __uint_as_float(__float_as_uint(q * up) | sb);
+    return code | (sb ? (uint32_t)F::sign : 0u);
+}
+
+// max over aligned groups of 8 lanes (quad swaps, then the half-row mirror)
+__device__ __forceinline__ uint32_t max8(uint32_t m) {
+    int x = (int)m;   // magnitudes: bit 31 clear, the integer order is the float order
+    x = max(x, __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false));
+    x = max(x, __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false));
+    x = max(x, __builtin_amdgcn_update_dpp(x, x, 0x141, 0xF, 0xF, false));
+    return (uint32_t)x;
+}
+
+// The wave's task.  vtotal padded elements; padded element v lies in row
+// t.row + v / lp at column t.col + v % lp (lp: the padded length of a row, or of the piece).
+template <int FMT, bool VEC>
+__device__ __forceinline__ void mx_task(const MxJob& J, const MxTask& t, float* edata, int lane) {
+    const int64_t row_len = J.row_len;
+    const int64_t lpr = J.nb * kMxBlock;   // padded row
+    int lp, nrows;
+    if (t.nrows > 0) {
+        lp = (int)lpr;
+        nrows = t.nrows;
+    } else {
+        const int64_t len = row_len - t.col < J.piece ? row_len - t.col : J.piece;
+        lp = (int)(ceil_div(len, kMxBlock) * kMxBlock);
+        nrows = 1;
+    }
+    const int vtotal = nrows * lp;
+    const uint32_t magic = 0xFFFFFFFFu / (uint32_t)lp + 1u;   // v / lp == umulhi(v, magic) for v * lp < 2^32
+    const int64_t vbase = t.row * lpr + t.col;                 // the task's first padded element of the tensor
+    const int64_t ebase = t.row * row_len + t.col;             // its first element
+    const int rl = (int)(row_len < (int64_t)1 << 30 ? row_len : (int64_t)1 << 30);   // nrows > 1: row_len <= lp
+    const int left0 = (int)(row_len - t.col < (int64_t)1 << 30 ? row_len - t.col : (int64_t)1 << 30);
+    // the task's own bases (wave-uniform): a lane adds 32-bit offsets below the task's size
+    const DFQ_GLOBAL float* src = (const DFQ_GLOBAL float*)J.src + ebase;
+    DFQ_GLOBAL float* dst = (DFQ_GLOBAL float*)J.dst + ebase;
+    DFQ_GLOBAL float* esum = (DFQ_GLOBAL float*)J.esum + ebase;   // khw == 1 (the LDS sums index from J.esum)
+    DFQ_GLOBAL uint8_t* codes = (DFQ_GLOBAL uint8_t*)J.codes + (FMT == DFQ_MX_FP4_E2M1 ? vbase >> 1 : vbase);
+    DFQ_GLOBAL uint8_t* scales = (DFQ_GLOBAL uint8_t*)J.scales + (vbase >> 5);
+    const bool want_d = J.dst != nullptr, want_c = J.codes != nullptr, want_s = J.scales != nullptr;
+    const bool want_e = J.esum != nullptr, lds_e = J.lds_esum != 0;
+
+    for (int v0 = 0; v0 < vtotal; v0 += 256 * kMxBatch) {
+        float x[kMxBatch][4];
+        int off[kMxBatch];       // element offset from the task's first element of the lane's first element
+        int nval[kMxBatch];      // its elements inside the row (0..4); VEC: 0 or 4
+#pragma unroll
+        for (int b = 0; b < kMxBatch; ++b) {
+            const int v = v0 + b * 256 + 4 * lane;
+            const int r = nrows > 1 ? (int)__umulhi((uint32_t)v, magic) : 0;
+            const int c = v - r * lp;   // column inside the task's row part
+            const int left = left0 - c;
+            nval[b] = v < vtotal ? (left >= 4 ? 4 : (left > 0 ? left : 0)) : 0;
+            off[b] = r * rl + c;
+            x[b][0] = x[b][1] = x[b][2] = x[b][3] = 0.f;   // padding behaves as +0
+            if (VEC) {
+                if (nval[b]) {
+                    const f32x4 q = *(const DFQ_GLOBAL f32x4*)(src + off[b]);
+                    x[b][0] = q.x; x[b][1] = q.y; x[b][2] = q.z; x[b][3] = q.w;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < nval[b]) x[b][j] = src[off[b] + j];
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < kMxBatch; ++b) {
+            const int v = v0 + b * 256 + 4 * lane;
+            if (v0 + b * 256 >= vtotal) break;   // wave-uniform
+            uint32_t m = __float_as_uint(x[b][0]) & 0x7fffffffu;
+#pragma unroll
+            for (int j = 1; j < 4; ++j) m = max(m, __float_as_uint(x[b][j]) & 0x7fffffffu);
+            m = max8(m);   // every lane takes part
+            const int X = mx_exponent<FMT>(m);
+            const float inv = pow2f(-X), up = pow2f(X);
+            float y[4];
+            uint32_t c[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) c[j] = mx_encode<FMT>(x[b][j], inv, up, y[j]);
+            if (v >= vtotal) continue;
+            // v numbers the task's padded elements: it addresses the codes and scales
+            if (want_c) {
+                if (FMT == DFQ_MX_FP4_E2M1) {
+                    const uint32_t lo = c[0] | (c[1] << 4), hi = c[2] | (c[3] << 4);
+                    if (VEC) {
+                        *(DFQ_GLOBAL uint16_t*)(codes + (v >> 1)) = (uint16_t)(lo | (hi << 8));
+                    } else {
+                        codes[v >> 1] = (uint8_t)lo;
+                        codes[(v >> 1) + 1] = (uint8_t)hi;
+                    }
+                } else {
+                    if (VEC) {
+                        *(DFQ_GLOBAL uint32_t*)(codes + v) = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) codes[v + j] = (uint8_t)c[j];
+                    }
+                }
+            }
+            if (want_s && (lane & 7) == 0) scales[v >> 5] = (uint8_t)(X + 127);
+            if (!nval[b]) continue;
+            const int eg = off[b];
+            float e[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) e[j] = y[j] - x[b][j];
+            if (VEC) {
+                if (want_d) {
+                    f32x4 q;
+                    q.x = y[0]; q.y = y[1]; q.z = y[2]; q.w = y[3];
+                    *(DFQ_GLOBAL f32x4*)(dst + eg) = q;
+                }
+                if (want_e && !lds_e) {
+                    f32x4 q;
+                    q.x = e[0]; q.y = e[1]; q.z = e[2]; q.w = e[3];
+                    *(DFQ_GLOBAL f32x4*)(esum + eg) = q;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (j >= nval[b]) break;
+                    if (want_d) dst[eg + j] = y[j];
+                    if (want_e && !lds_e) esum[eg + j] = e[j];
+                }
+            }
+            if (lds_e) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < nval[b]) edata[off[b] + j] = e[j];
+            }
+        }
+    }
+    if (lds_e) {
+        // E[p] = sum_k e[p * khw + k] in torch.sum(e.view(O, I, khw), -1)'s order: the task holds
+        // whole khw groups (rows, or pieces that are multiples of khw)
+        wave_lds_sync();
+        const int khw = J.khw;
+        const int n = t.nrows > 0 ? (int)(nrows * row_len) : (int)(row_len - t.col < J.piece ? row_len - t.col : J.piece);
+        const int np = n / khw;
+        DFQ_GLOBAL float* out = (DFQ_GLOBAL float*)J.esum + ebase / khw;
+        if (khw == 9) {
+            for (int pi = lane; pi < np; pi += kWave) {
+                const float* e = edata + pi * 9;
+                out[pi] = aten_inner_sum([&](int64_t k) { return e[k]; }, (int64_t)9);
+            }
+        } else {
+            for (int pi = lane; pi < np; pi += kWave) {
+                const float* e = edata + pi * khw;
+                out[pi] = aten_inner_sum([&](int64_t k) { return e[k]; }, (int64_t)khw);
+            }
+        }
+        wave_lds_sync();   // the copy is rewritten by the wave's next task
+    }
+}
+
+// LDS (dynamic): DFQ_MX_ESUM_TASK_ELEMS floats per wave when some tensor's error sums
+// need them, none otherwise; written and read by its own wave only.
+__global__ __launch_bounds__(kThreads) void mx_quantize_kernel(const MxJob* __restrict__ jobs,
+                                                               const MxTask* __restrict__ tasks, int64_t n_tasks) {
+    extern __shared__ __attribute__((aligned(16))) float mx_lds[];
+    float* const edata = mx_lds + (threadIdx.x >> 6) * DFQ_MX_ESUM_TASK_ELEMS;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t wave = (int64_t)blockIdx.x * kMxWaves + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kMxWaves;
+    for (int64_t ti = wave; ti < n_tasks; ti += n_waves) {
+        const MxTask t = tasks[ti];
+        const MxJob J = jobs[t.job];
+        if (J.format == DFQ_MX_FP4_E2M1) {
+            if (J.vec) mx_task<DFQ_MX_FP4_E2M1, true>(J, t, edata, lane);
+            else mx_task<DFQ_MX_FP4_E2M1, false>(J, t, edata, lane);
+        } else {
+            if (J.vec) mx_task<DFQ_MX_FP8_E4M3, true>(J, t, edata, lane);
+            else mx_task<DFQ_MX_FP8_E4M3, false>(J, t, edata, lane);
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t preload_mx() {   // see dfq_preload
+    hipFuncAttributes a;
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(mx_quantize_kernel));
+}
+
+}  // namespace dfq
+
+using namespace dfq;
+
+extern "C" int dfq_mx_quantize_batch(const dfq_mx_desc* d, int32_t n, void* ws, int64_t ws_bytes, void* stream) {
+    if (n < 0 || (n > 0 && !d)) return DFQ_ERR_INVALID;
+    if (n == 0) return DFQ_OK;
+    MxLayout L;
+    std::vector<MxTask> tasks;
+    const int rc = mx_plan(d, n, L, tasks);
+    if (rc != DFQ_OK) return rc;
+    if (!ws || ws_bytes < L.total) return DFQ_ERR_WORKSPACE;
+    if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return DFQ_ERR_INVALID;
+    char* base = static_cast<char*>(ws);
+    std::vector<char> blob((size_t)L.total, 0);   // one staging blob (jobs, tasks), one copy
+    MxJob* hj = reinterpret_cast<MxJob*>(blob.data() + L.o_jobs);
+    for (int32_t p = 0; p < n; ++p)
+        hj[p] = MxJob{d[p].src, d[p].dst, d[p].codes, d[p].scales, d[p].esum, d[p].row_len, mx_blocks(d[p].row_len),
+                      mx_split(d[p]) ? mx_piece_len(d[p]) : 0, d[p].khw, d[p].format, mx_vec(d[p]) ? 1 : 0,
+                      mx_lds_esum(d[p]) ? 1 : 0};
+    std::memcpy(blob.data() + L.o_tasks, tasks.data(), sizeof(MxTask) * tasks.size());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DFQ_HIP_CHECK(stage_h2d(base, blob.data(), blob.size(), s));
+    // one wave per task up to 2^18 tasks: blocks dispatched as others retire balance the uneven tasks
+    const int grid = (int)std::min<int64_t>(ceil_div(L.n_tasks, (int64_t)kMxWaves), 1 << 16);
+    const size_t lds = L.lds_jobs > 0 ? sizeof(float) * kMxWaves * DFQ_MX_ESUM_TASK_ELEMS : 0;
+    hipLaunchKernelGGL(mx_quantize_kernel, dim3(grid), dim3(kThreads), lds, s,
+                       reinterpret_cast<const MxJob*>(base + L.o_jobs),
+                       reinterpret_cast<const MxTask*>(base + L.o_tasks), L.n_tasks);
+    DFQ_LAUNCH_CHECK();
+    return DFQ_OK;
+}

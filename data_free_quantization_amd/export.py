@@ -10,6 +10,12 @@ uint8 / int16, or packed nibbles; asymmetric codes above 8 bits are unsigned
 metadata (bits, granularity, symmetric, clip, shapes).  ``load(path)`` returns
 the tensors; ``dequantize(entry)`` rebuilds the fp32 weight exactly as the sweep
 did: ``clamp(fl(fl(q * s) + zero), clip)``.
+
+With ``weight_format="mxfp4"`` / ``"mxfp8"`` (an MX state of ``quantize_targ_layer``)
+the file holds ``k.codes`` (uint8 [rows, nb, 16] packed FP4 nibbles or [rows, nb, 32]
+FP8 bytes), ``k.scales`` (uint8 E8M0 [rows, nb], one per 32 elements of a row) and
+``k.bias``; the metadata adds ``weight_format`` and ``mx_block``, and ``dequantize``
+dispatches on it (``mx.mx_dequantize``: ``+-q * 2^(scale - 127)``, exact).
 """
 from __future__ import annotations
 
@@ -22,7 +28,10 @@ from safetensors.torch import load_file, save_file
 
 
 def save(path, graph, state: Dict, *, bits: int, granularity: str, symmetric: bool,
-         clip: Optional[Sequence[float]] = None, packed: bool = False) -> Dict[str, dict]:
+         clip: Optional[Sequence[float]] = None, packed: bool = False, weight_format: str = "int") -> Dict[str, dict]:
+    from . import mx
+    if mx.is_mx(weight_format):
+        return _save_mx(path, graph, state, weight_format, clip)
     tensors, layers = {}, {}
     for key, st in state.items():
         layer = graph[key]
@@ -43,8 +52,29 @@ def save(path, graph, state: Dict, *, bits: int, granularity: str, symmetric: bo
     return layers
 
 
+def _save_mx(path, graph, state, weight_format, clip):
+    from . import mx
+    tensors, layers = {}, {}
+    for key, st in state.items():
+        if st.get("format") != weight_format:
+            raise ValueError("layer %s: the state holds %r, not %r" % (key, st.get("format", "int"), weight_format))
+        layer = graph[key]
+        k = str(key)
+        tensors[f"{k}.codes"] = st["codes"].detach().contiguous()
+        tensors[f"{k}.scales"] = st["scales"].detach().contiguous()
+        if layer.bias is not None:
+            tensors[f"{k}.bias"] = layer.bias.detach().contiguous()
+        layers[k] = {"shape": list(layer.weight.shape), "type": type(layer).__name__}
+    meta = {"format": "dfq-mi355x/1", "weight_format": weight_format, "mx_block": mx.BLOCK,
+            "bits_per_weight": mx.bits_per_weight(weight_format), "clip": list(clip) if clip is not None else None,
+            "code_storage": "fp4_nibbles" if weight_format == "mxfp4" else "fp8_e4m3", "layers": layers}
+    save_file({n: t.cpu() for n, t in tensors.items()}, str(path), metadata={"dfq": json.dumps(meta)})
+    return layers
+
+
 def load(path, device="cpu"):
-    """(meta, {layer key: {codes, scale, zero[, bias]}}) from a file written by save()."""
+    """(meta, {layer key: {codes, scale, zero[, bias]}}) from a file written by save()
+    ({codes, scales[, bias]} for an MX file)."""
     from safetensors import safe_open
     with safe_open(str(path), framework="pt") as f:
         meta = json.loads(f.metadata()["dfq"])
@@ -59,6 +89,12 @@ def load(path, device="cpu"):
 def dequantize(meta: dict, key: str, entry: Dict[str, torch.Tensor]) -> torch.Tensor:
     """fp32 weight of one exported layer, bit-identical to the sweep's output."""
     shape = meta["layers"][key]["shape"]
+    if meta.get("weight_format", "int") != "int":
+        from . import mx
+        y = mx.mx_dequantize(entry["codes"], entry["scales"], shape, meta["weight_format"])
+        if meta.get("clip") is not None:   # clip_weight as its own stage after the MX pass
+            y = y.clamp(meta["clip"][0], meta["clip"][1])
+        return y
     q = entry["codes"]
     n = 1
     for s in shape:

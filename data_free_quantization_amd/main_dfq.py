@@ -25,6 +25,12 @@ Same flags and stage order; the transforms run on the GPU.  Additive flags:
                        The defaults (16, 0.5) are interface choices: no dataset ships
                        here to tune them on.  --report then counts, per layer, the units
                        that chose a narrower range and those at the narrowest candidate
+  --weight_format {int,mxfp4,mxfp8}   int (default): the integer grid of --bits_weight /
+                       --granularity / --symmetric.  mxfp4 / mxfp8: OCP MX block-scaled
+                       weights (mx.py: FP4 E2M1 / FP8 E4M3 elements, one power-of-two scale
+                       per 32 elements of a row; 4.25 / 8.25 bits per weight), to which those
+                       three flags do not apply.  Not with --clip_search, --bc_mode reference,
+                       --clip_weight under --bc_mode fused, or --world_size > 1
 
 Example (README.md:137 of the reference):
   python -m data_free_quantization_amd.main_dfq --task cls --relu --equalize --absorption \
@@ -40,7 +46,7 @@ import time
 import torch
 import torch.nn as nn
 
-from . import _lib, zoo
+from . import _lib, mx, zoo
 from .bias_absorption import bias_absorption
 from .bias_correction import bias_correction
 from .clip_weight import clip_weight, search_clip
@@ -92,7 +98,23 @@ def get_argument(argv=None):
     p.add_argument("--clip_candidates", type=int, default=16, help="candidate ranges per unit (1..64)")
     p.add_argument("--clip_min_frac", type=float, default=0.5,
                    help="the narrowest candidate as a share of the min-max range, in [0, 1]")
+    p.add_argument("--weight_format", default="int", choices=["int", "mxfp4", "mxfp8"],
+                   help="weight codes: the integer grid, or OCP MX block-scaled FP4 / FP8 (32-element blocks)")
     args = p.parse_args(argv)
+    if args.weight_format != "int":
+        if not args.quantize:
+            p.error("--weight_format needs --quantize")
+        if args.clip_search:
+            p.error("--weight_format %s conflicts with --clip_search (the search minimizes an integer grid's noise)"
+                    % args.weight_format)
+        if args.bc_mode == "reference":
+            p.error("--weight_format %s conflicts with --bc_mode reference (its error term is the integer "
+                    "quantizer's)" % args.weight_format)
+        if args.clip_weight and args.bc_mode == "fused":
+            p.error("--weight_format %s conflicts with --clip_weight under --bc_mode fused (the MX pass has no fused "
+                    "clamp)" % args.weight_format)
+        if args.world_size > 1:
+            p.error("--weight_format %s is not sharded: run it with --world_size 1" % args.weight_format)
     if args.report and not args.quantize:
         p.error("--report needs --quantize")
     if args.clip_search and not args.quantize:
@@ -216,7 +238,8 @@ def main(argv=None):
     if args.quantize:
         set_layer_bits(graph, args.bits_weight, args.bits_activation, args.bits_bias, targ_layer)
         sharded = args.world_size > 1
-        fold_ranges = {} if (args.granularity == "tensor" and not sharded) else None
+        mx_fmt = args.weight_format != "int"
+        fold_ranges = {} if (args.granularity == "tensor" and not sharded and not mx_fmt) else None
         model = merge_batchnorm(model, graph, bottoms, targ_layer, ranges=fold_ranges)
         fused_clip = [-15, 15] if (args.clip_weight and args.bc_mode == "fused") else None
         if args.report:   # the weights the quantizer is about to see (every rank: same stage order)
@@ -229,7 +252,8 @@ def main(argv=None):
                                    targ_type=targ_layer, weight_ranges=fold_ranges)
         graph = quantize_targ_layer(graph, args.bits_weight, args.bits_bias, targ_layer,
                                     granularity=args.granularity, symmetric=args.symmetric, clip=fused_clip,
-                                    state=state, shard=sharded, weight_ranges=fold_ranges)
+                                    state=state, shard=sharded, weight_ranges=fold_ranges,
+                                    **({"weight_format": args.weight_format} if mx_fmt else {}))
         set_quant_minmax(graph, bottoms)   # main_dfq.py:217
     if args.clip_weight and not (args.quantize and args.bc_mode == "fused"):
         clip_weight(graph, range_clip=[-15, 15], targ_type=targ_layer)
@@ -246,7 +270,8 @@ def main(argv=None):
         from . import export
         clip = [-15, 15] if args.clip_weight else None   # fused in the sweep or clip_weight after it: same clamp
         export.save(args.export, graph, state, bits=args.bits_weight, granularity=args.granularity,
-                    symmetric=args.symmetric, clip=clip)
+                    symmetric=args.symmetric, clip=clip,
+                    **({"weight_format": args.weight_format} if args.weight_format != "int" else {}))
         print(f"Exported {len(state)} quantized layers to {args.export}")
     if args.report and rank == 0:   # sharded runs: every rank holds every result after the gather
         import json
@@ -256,7 +281,9 @@ def main(argv=None):
             "clip": args.clip_weight, "clip_range": [-15.0, 15.0], "bc_mode": args.bc_mode,
             "world_size": args.world_size,
             **({"clip_search": True, "clip_candidates": args.clip_candidates, "clip_min_frac": args.clip_min_frac}
-               if args.clip_search else {})}, clip_search=searched)
+               if args.clip_search else {}),
+            **({"weight_format": args.weight_format, "bits_per_weight": mx.bits_per_weight(args.weight_format)}
+               if args.weight_format != "int" else {})}, clip_search=searched)
         with open(args.report, "w") as f:
             json.dump(rep, f, indent=1, allow_nan=False)
         m = rep["model"]

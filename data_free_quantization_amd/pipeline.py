@@ -35,7 +35,7 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
             bits_weight: int = 8, bits_activation: int = 8, bits_bias: int = 8, granularity: str = "tensor",
             symmetric: bool = False, bc_mode: str = "literal", clip_range=(-15, 15),
             stage_hook: Optional[Callable[[str], None]] = None, timings: Optional[Dict] = None,
-            report: Optional[dict] = None, clip_search: Optional[dict] = None):
+            report: Optional[dict] = None, clip_search: Optional[dict] = None, weight_format: str = "int"):
     """Run the DFQ stages on ``model`` (already on the GPU) in place; returns the
     equalization relations.  ``report``: a dict to fill with the quality report
     (quality.weight_report) of the quantized weights against their values after
@@ -45,7 +45,26 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
     minimizes its own quantization noise (clip_weight.search_clip; stage
     "clipsearch", after the report's snapshot, so the report measures the noise
     against the unclamped weights); needs ``quantize``.  Bias correction sees the
-    clamped weight as its input."""
+    clamped weight as its input.
+    ``weight_format``: "int" (the integer grid of ``bits_weight`` / ``granularity`` /
+    ``symmetric``), or "mxfp4" / "mxfp8": OCP MX block-scaled weights (mx.py), to which
+    those three do not apply.  An MX format raises ValueError with ``clip_search`` (the
+    search measures integer grids), with ``bc_mode="reference"`` (its error term is the
+    integer quantizer's) and with ``clip`` under ``bc_mode="fused"`` (the MX pass has no
+    fused clamp); ``clip`` as its own stage after quantization stays, in the reference's
+    order."""
+    from .mx import bits_per_weight, is_mx
+    mx_fmt = is_mx(weight_format)
+    if mx_fmt:
+        if clip_search is not None:
+            raise ValueError("weight_format=%r conflicts with clip_search: the search minimizes an integer "
+                             "grid's noise" % weight_format)
+        if correction and bc_mode == "reference":
+            raise ValueError("weight_format=%r conflicts with bc_mode='reference': its error term is the integer "
+                             "quantizer's (use 'fused' or 'literal')" % weight_format)
+        if clip and bc_mode == "fused":
+            raise ValueError("weight_format=%r conflicts with clip under bc_mode='fused': the MX pass has no fused "
+                             "clamp" % weight_format)
     assert relu or relu == equalize, "must replace relu6 to relu while equalization"
     assert equalize or absorption == equalize, "must use absorption with equalize"
     t = timings if timings is not None else {}
@@ -80,7 +99,7 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
     if quantize:
         set_layer_bits(graph, bits_weight, bits_activation, bits_bias, targ)
         # the second fold hands the folded weights' ranges to the quantize sweep
-        fold_ranges = {} if granularity == "tensor" else None
+        fold_ranges = {} if (granularity == "tensor" and not mx_fmt) else None
         stage("bn2", merge_batchnorm, model, graph, bottoms, targ, ranges=fold_ranges)
         fused_clip = tuple(clip_range) if (clip and bc_mode == "fused") else None
         if report is not None:
@@ -93,14 +112,17 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
                              symmetric=symmetric, candidates=cs_cfg["clip_candidates"],
                              min_frac=cs_cfg["clip_min_frac"], targ_type=targ, weight_ranges=fold_ranges)
         stage("quant", quantize_targ_layer, graph, bits_weight, bits_bias, targ, granularity=granularity,
-              symmetric=symmetric, clip=fused_clip, state=state, weight_ranges=fold_ranges)
+              symmetric=symmetric, clip=fused_clip, state=state, weight_ranges=fold_ranges,
+              **({"weight_format": weight_format} if mx_fmt else {}))
     if clip and not (quantize and bc_mode == "fused"):
         stage("clip", clip_weight, graph, range_clip=list(clip_range), targ_type=targ)
     if snap is not None:   # the weights are final from here (bias correction rewrites biases only)
         report.update(quality.weight_report(graph, snap, config={
             "bits_weight": bits_weight, "granularity": granularity, "symmetric": bool(symmetric),
             "equalize": bool(equalize), "absorption": bool(absorption), "clip": bool(clip),
-            "clip_range": [float(c) for c in clip_range], "bc_mode": bc_mode, **cs_cfg}, clip_search=searched))
+            "clip_range": [float(c) for c in clip_range], "bc_mode": bc_mode, **cs_cfg,
+            **({"weight_format": weight_format, "bits_per_weight": bits_per_weight(weight_format)} if mx_fmt else {})},
+            clip_search=searched))
     if correction:
         err = None
         if bc_mode == "fused":

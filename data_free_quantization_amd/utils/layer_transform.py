@@ -206,7 +206,7 @@ def _identity_forward(bn):
 
 def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, *, granularity="tensor",
                         symmetric=False, clip=None, state: Optional[Dict] = None, shard: bool = False,
-                        group=None, weight_ranges: Optional[Dict] = None):
+                        group=None, weight_ranges: Optional[Dict] = None, weight_format: str = "int"):
     """Fake-quantize every target layer's weight (and bias when bits_bias < 32) in
     place, all layers in one grouped launch.
 
@@ -225,7 +225,20 @@ def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, *, gr
     every rank holding the model): each rank sweeps its LPT share of the tensors
     into its slab of an output arena, one in-place all-gather (RCCL) gives every
     rank every result, and each rank writes them back into its parameters
-    (distributed.ShardedSweep).  Results are identical to the unsharded call."""
+    (distributed.ShardedSweep).  Results are identical to the unsharded call.
+
+    ``weight_format="mxfp4"`` / ``"mxfp8"``: the weights take OCP MX block-scaled
+    codes instead of an integer grid (mx.mx_quantize: FP4 / FP8 elements, one
+    power-of-two scale per 32 elements of a row; all layers in one launch);
+    ``bit_weight``, ``granularity`` and ``symmetric`` then do not apply to them, and
+    ``clip``, ``shard=True`` and ``weight_ranges`` raise ValueError.  Biases take the
+    integer sweep at ``bits_bias`` as always.  ``state[k]`` holds ``codes``, ``scales``,
+    ``esum``, ``khw`` and ``format``; each layer is marked (``layer.weight_format``) so
+    that the Quant* layers' forward uses the stored weight as it is."""
+    from ..mx import is_mx
+    if is_mx(weight_format):
+        return _quantize_targ_layer_mx(graph, bits_bias, targ_type, weight_format, clip=clip, state=state,
+                                       shard=shard, weight_ranges=weight_ranges)
     _lib.weights_changed()
     if shard and torch.distributed.is_initialized():
         return _quantize_targ_layer_sharded(graph, bit_weight, bits_bias, targ_type, granularity=granularity,
@@ -243,6 +256,7 @@ def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, *, gr
     for layer_idx, layer in graph.items():
         if type(layer) not in tt:
             continue
+        layer.__dict__.pop("weight_format", None)   # an earlier MX pass's mark
         lp = layer._parameters   # no Module.__getattr__ per access
         w = lp["weight"]   # written in place by the kernel: no .data view needed
         rows = w.size(0) if per_channel else 1
@@ -283,6 +297,68 @@ def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, *, gr
         wk = [k for k in keys if k is not None]
         for k, it, sp in zip(wk, wl, spans):
             state[k] = _StateEntry(codes, f32, sp, tuple(it.src.shape), it.khw, up)
+    return graph
+
+
+def _quantize_targ_layer_mx(graph, bits_bias, targ_type, weight_format, *, clip, state, shard, weight_ranges):
+    """quantize_targ_layer with an MX weight format (see there)."""
+    from .. import mx
+    if clip is not None:
+        raise ValueError("weight_format=%r has no fused clamp: clip does not apply to MX weights" % weight_format)
+    if shard:
+        raise ValueError("weight_format=%r is not sharded: shard=True does not apply to MX weights" % weight_format)
+    if weight_ranges is not None:
+        raise ValueError("weight_format=%r takes no per-tensor range: weight_ranges does not apply to MX weights"
+                         % weight_format)
+    _lib.weights_changed()
+    print("Quantizing Layer parameters")
+    if bits_bias == 32:
+        print("Skipping bias quantization (32 bits)")
+    assert targ_type is not None, "targ_type cannot be None!"
+    tt = tuple(targ_type)
+    items, keys, layers, biases = [], [], [], []
+    for layer_idx, layer in graph.items():
+        if type(layer) not in tt:
+            continue
+        lp = layer._parameters
+        w = lp["weight"]
+        items.append(mx.MXItem(src=w, dst=w, fmt=weight_format, khw=khw_of(w), rows=w.size(0)))
+        keys.append(layer_idx)
+        layers.append(layer)
+        if lp.get("bias") is not None and bits_bias < 32:
+            b = lp["bias"]
+            biases.append(SweepItem(src=b, dst=b, bits=bits_bias, per_channel=False, symmetric=False, rows=1))
+    if not items:
+        return graph
+    spans = None
+    if state is not None:   # codes / scales / E of every layer in three allocations
+        dev = items[0].src.device
+        cbytes = mx.FORMATS[weight_format][2]
+        up = lambda k: -(-k // 16) * 16   # noqa: E731  -- 16-element aligned pieces (vector paths)
+        spans, co, so, fo = [], 0, 0, 0
+        for it in items:
+            nb = mx.blocks(it.src.numel() // it.rows)
+            ne = it.src.numel() // it.khw
+            spans.append((co, so, fo, it.rows, nb, ne))
+            co += it.rows * nb * cbytes
+            so += up(it.rows * nb)
+            fo += up(ne)
+        codes = torch.empty(co, dtype=torch.uint8, device=dev)
+        scales = torch.empty(so, dtype=torch.uint8, device=dev)
+        f32 = torch.empty(fo, dtype=torch.float32, device=dev)
+        for it, (c0, s0, f0, r, nb, ne) in zip(items, spans):   # raw addresses: the views are made below
+            it.codes, it.scales, it.esum = codes.data_ptr() + c0, scales.data_ptr() + s0, f32.data_ptr() + 4 * f0
+    mx.mx_quantize(items)
+    if biases:
+        plan = SweepPlan(biases)
+        plan.execute()
+        plan.destroy()
+    for layer in layers:   # the Quant* layers' forward takes a marked layer's weight as stored
+        layer.__dict__["weight_format"] = weight_format
+    if state is not None:
+        for k, it, (c0, s0, f0, r, nb, ne) in zip(keys, items, spans):
+            state[k] = dict(codes=codes[c0:c0 + r * nb * cbytes].view(r, nb, cbytes), scales=scales[s0:s0 + r * nb].view(r, nb),
+                            esum=f32[f0:f0 + ne], khw=it.khw, format=weight_format)
     return graph
 
 
@@ -352,6 +428,7 @@ def _quantize_targ_layer_sharded(graph, bit_weight, bits_bias, targ_type, *, gra
         layer = graph[layer_idx]
         if type(layer) not in targ_type:
             continue
+        layer.__dict__.pop("weight_format", None)   # an earlier MX pass's mark
         lp = layer._parameters
         w = lp["weight"].data
         _lib.require_device(w)

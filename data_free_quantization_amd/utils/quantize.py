@@ -366,6 +366,9 @@ class _QuantWeightMixin:
     fake-quant with float(min)/float(max), bias fake-quant with the data range."""
 
     def _qparams(self, weight, bias):
+        # a layer quantize_targ_layer left in an MX format (weight_format="mxfp4" / "mxfp8") holds
+        # its block-scaled values already: a per-tensor integer grid would move them
+        mx = self.__dict__.get("weight_format", "int") != "int"
         if _no_autograd(weight, bias):
             # inference: float(weight.min()) / float(weight.max()) and the bias's own
             # 0-d fp32 range stay on the device (dfq_range), one async launch each.
@@ -388,7 +391,7 @@ class _QuantWeightMixin:
             words = bufs.get((weight.device, stream.value))
             if words is None:
                 words = bufs[(weight.device, stream.value)] = torch.zeros(16, dtype=torch.int32, device=weight.device)
-            qweight = fake_quant_tensor(weight, self.num_bits, words=words[:8])
+            qweight = weight if mx else fake_quant_tensor(weight, self.num_bits, words=words[:8])
             qbias = None
             if bias is not None:
                 qbias = fake_quant_tensor(bias, self.num_bits_bias, scale_f32=True, words=words[8:])
@@ -397,8 +400,8 @@ class _QuantWeightMixin:
             else:
                 self.__dict__.pop("_qw_cache", None)
             return qweight, qbias
-        qweight = quantize(weight, num_bits=self.num_bits, min_value=float(weight.min()),
-                           max_value=float(weight.max()))
+        qweight = weight if mx else quantize(weight, num_bits=self.num_bits, min_value=float(weight.min()),
+                                             max_value=float(weight.max()))
         qbias = quantize(bias, num_bits=self.num_bits_bias) if bias is not None else None
         return qweight, qbias
 

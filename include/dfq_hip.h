@@ -421,6 +421,65 @@ int64_t dfq_clip_search_ws_bytes(const dfq_clip_search_desc* descs, int32_t n);
  * weight at most once per call.  n == 0: DFQ_OK, nothing launched. */
 int dfq_clip_search_batch(const dfq_clip_search_desc* descs, int32_t n, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- OCP Microscaling (MX) block-scaled weight quantization (no reference
+ *      counterpart; the operand format of CDNA4's scaled matrix instructions) ----
+ * Every row of the [rows, row_len] view is cut into blocks of DFQ_MX_BLOCK = 32
+ * consecutive elements, nb = ceil(row_len / 32) per row (blocks never cross rows; a
+ * last partial block behaves as if padded with +0).  Element formats: FP4 E2M1
+ * (magnitudes 0 0.5 1 1.5 2 3 4 6, emax 2) and FP8 E4M3 "fn" (bias 7, subnormals,
+ * maximum 448, no infinities, emax 8).  For one block of fp32 elements x_i:
+ *   amax = max |x_i|;  X = amax == 0 ? -127 : clamp(floor(log2 amax) - emax, -127, 127)
+ *   scale byte = X + 127 (E8M0; 0xFF is never written)
+ *   q_i  = |x_i| * 2^-X rounded to the nearest magnitude of the format, ties to the
+ *          even code, saturating at the maximum (6 or 448; no E4M3 NaN code)
+ *   code = the sign bit of x_i (kept by -0 and by values that round to zero) above
+ *          q_i's encoding: a nibble `s e e m`, or a byte `s eeee mmm`
+ *   y_i  = +-q_i * 2^X (exact in fp32)
+ * Outputs, each optional (not all NULL):
+ *   dst    fp32 y, [rows, row_len]; may alias src
+ *   codes  uint8 [rows, nb, 16] (FP4: element 2k in the low nibble, 2k+1 in the high
+ *          one) or [rows, nb, 32] (FP8); the padding of a partial block is +0 codes
+ *   scales uint8 [rows, nb]
+ *   esum   fp32 [rows * row_len / khw], the sweep's E[p] = sum_{k<khw} fl32(y - x)[p*khw + k]
+ *          in ATen's CPU order; row_len % khw != 0 with esum set: DFQ_ERR_SHAPE
+ * Contract domain: finite inputs whose non-zero magnitudes are >= 2^-100.  A
+ * tensor's result is the same bits from run to run, whatever the rest of the list or
+ * its place in it: a block's result depends on its 32 elements alone, every error sum
+ * is added by one lane in a fixed order, and no atomic is used. */
+enum { DFQ_MX_BLOCK = 32 };
+enum { DFQ_MX_FP4_E2M1 = 0, DFQ_MX_FP8_E4M3 = 1 };
+/* Elements one wave task holds at most; with esum and khw > 1 (the errors wait in
+ * LDS for their sums) DFQ_MX_ESUM_TASK_ELEMS.  A row longer than that is cut into
+ * pieces that are multiples of 32 and, with such an esum, of khw: when no such
+ * piece fits (lcm(32, khw) > DFQ_MX_ESUM_TASK_ELEMS) the call returns
+ * DFQ_ERR_UNSUPPORTED; every khw <= 64 and every row that fits one task are served. */
+enum { DFQ_MX_TASK_ELEMS = 4096, DFQ_MX_ESUM_TASK_ELEMS = 2048 };
+typedef struct dfq_mx_desc {
+    const float* src;      /* 4-B aligned */
+    float*       dst;      /* may be NULL, may alias src */
+    uint8_t*     codes;    /* may be NULL */
+    uint8_t*     scales;   /* may be NULL */
+    float*       esum;     /* may be NULL */
+    int64_t      rows;     /* >= 1 */
+    int64_t      row_len;  /* >= 1 */
+    int32_t      khw;      /* >= 1; spatial size for esum (1 for Linear / 1x1) */
+    int32_t      format;   /* DFQ_MX_FP4_E2M1 | DFQ_MX_FP8_E4M3 */
+    int32_t      flags;    /* 0 */
+    int32_t      reserved;
+} dfq_mx_desc;
+/* Device workspace bytes for dfq_mx_quantize_batch (-1: bad arguments). */
+int64_t dfq_mx_quantize_ws_bytes(const dfq_mx_desc* descs, int32_t n);
+/* Every tensor of the list in one launch and one HBM pass, asynchronous on `stream`,
+ * no host wait (the tables go up through the library's pinned staging ring).  ws as
+ * for dfq_clip_search_batch: >= dfq_mx_quantize_ws_bytes bytes, 256-B aligned,
+ * stream-ordered with `stream`; DFQ_ERR_WORKSPACE if it is NULL or too small,
+ * DFQ_ERR_INVALID if it is misaligned or a descriptor is bad (format, non-zero flags,
+ * sizes, khw < 1, a NULL or misaligned src, dst or esum not 4-B aligned, every output
+ * NULL).  Rows whose start is 16-B aligned (src, dst and esum 16-B aligned, codes
+ * 4-B aligned, row_len % 4 == 0) take 16-B loads; the others a 4-B path with the
+ * same results.  Each tensor at most once per call.  n == 0: DFQ_OK, nothing launched. */
+int dfq_mx_quantize_batch(const dfq_mx_desc* descs, int32_t n, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- high-bias absorption (bias_absorption.py:147-197) ------------------
  * c = max(bn_b - N*bn_w, 0) (bn_* = the BN's fake_weight / fake_bias);
  * b2[o] += sum_i (sum_k W2[o,i,k]) * c[g*i2 + i];  b1 -= c;  bn_b -= c.

@@ -1,0 +1,163 @@
+"""Time dfq_mx_quantize_batch on the bench headline's list, beside the sweep.
+
+The list is bench.py's: 155 MobileNetV2 weight sets (8,215 tensors, 2.15 GB of fp32
+weights), seeded as there.  Each MX format writes dst + codes + scales + esum for
+every tensor in one call (one launch, one HBM pass); dst and esum are the sweep
+items' own buffers, so both passes write the same places.  The yardstick is the
+bench's sweep (per-channel INT8 with its codes and error sums) on the same list, in
+the same process, alternated three times with the MX calls; every timed call sits
+inside a HIP event pair (the table upload and the launch), median of --steps calls
+after --warmup.  Fractions are algorithmic bytes (computed here from the shapes:
+read 4, write 4 + 0.5 | 1 of codes + 1/32 of scales per padded element + 4/khw of
+error sums) over time over the 8 TB/s HBM peak; the sweep's are its plan's
+algo_bytes.  A whole call over peak is an end-to-end figure (it holds the table
+upload), not the kernel's share.  One weight set alone is timed the same way, in
+microseconds.  The JSON line goes to stdout and to --out.
+
+  python scripts/mx_quantize_time.py             # -> profiles/r09/mx_quantize_time.jsonl
+  python scripts/mx_quantize_time.py --quality   # MobileNetV2 model SQNR per format, with and
+                                                 #   without equalization -> profiles/r09/quality_mx.jsonl
+"""
+import argparse
+import ctypes as C
+import json
+import statistics
+import sys
+from pathlib import Path
+
+import numpy as np
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+import bench  # noqa: E402
+from data_free_quantization_amd import _lib, distributed as D, mx  # noqa: E402
+
+OUT = Path(__file__).resolve().parent.parent / "profiles" / "r09"
+
+
+def emit(records, path):
+    lines = [json.dumps(r) for r in records]
+    print("\n".join(lines))
+    path.parent.mkdir(parents=True, exist_ok=True)
+    path.write_text("\n".join(lines) + "\n")
+
+
+def timed(run, stream, warmup, steps):
+    for _ in range(warmup):
+        run()
+    return statistics.median(bench.steps_with_events(run, stream, steps))
+
+
+class MxCall:
+    """A prepared dfq_mx_quantize_batch call over sweep items: the descriptor table,
+    the code and scale arenas and the workspace; run() is the one C call."""
+
+    def __init__(self, items, fmt):
+        dev = items[0].src.device
+        cb = mx.FORMATS[fmt][2]
+        geo = []
+        for it in items:
+            rows = it.src.shape[0]
+            geo.append((rows, it.src.numel() // rows, mx.blocks(it.src.numel() // rows)))
+        self.codes = torch.empty(sum(r * nb * cb for r, _, nb in geo), dtype=torch.uint8, device=dev)
+        self.scales = torch.empty(sum(-(-r * nb // 16) * 16 for r, _, nb in geo), dtype=torch.uint8, device=dev)
+        tab, co, so, self.algo_bytes = [], 0, 0, 0
+        for it, (rows, row_len, nb) in zip(items, geo):
+            tab.append((it.src.data_ptr(), it.dst.data_ptr(), self.codes.data_ptr() + co, self.scales.data_ptr() + so,
+                        it.esum.data_ptr() if it.esum is not None else 0, rows, row_len, it.khw, mx.FORMATS[fmt][0], 0, 0))
+            co += rows * nb * cb
+            so += -(-rows * nb // 16) * 16
+            self.algo_bytes += 8 * rows * row_len + rows * nb * (cb + 1) + (4 * rows * row_len // it.khw
+                                                                           if it.esum is not None else 0)
+        self._tab = np.array(tab, dtype=mx._MX)
+        self._descs = self._tab.ctypes.data_as(C.POINTER(_lib.MxDesc))
+        self._n = len(items)
+        nb_ws = int(_lib.load().dfq_mx_quantize_ws_bytes(self._descs, self._n))
+        assert nb_ws > 0
+        self._ws = torch.empty(nb_ws, dtype=torch.uint8, device=dev)
+        self.ws_bytes = nb_ws
+
+    def run(self, stream):
+        _lib.check(_lib.load().dfq_mx_quantize_batch(self._descs, self._n, self._ws.data_ptr(), self._ws.numel(),
+                                                     C.c_void_p(stream.cuda_stream)), "dfq_mx_quantize_batch")
+
+
+def timing(args):
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    _lib.preload()
+    b = bench.parse([])
+    shapes = bench.model_shapes(b.model)
+    per_copy = sum(int(torch.Size(s).numel()) for s in shapes)
+    copies = args.copies or max(1, -(-(2 << 30) // (4 * per_copy)))
+    per_channel, symmetric = b.granularity == "channel", not b.asym
+    specs = D.uniform_specs(shapes * copies, bits=b.bits, per_channel=per_channel, symmetric=symmetric,
+                            want_esum=not b.no_esum, clip=(-15.0, 15.0))
+    items = bench.make_list(specs, range(len(specs)), dev, 1234)
+    plan = bench._plan_of(items)
+    stream = torch.cuda.current_stream(dev)
+    calls = {fmt: MxCall(items, fmt) for fmt in mx.FORMATS}
+    ones = {fmt: MxCall(items[:len(shapes)], fmt) for fmt in mx.FORMATS}
+    one_plan = bench._plan_of(items[:len(shapes)])
+    legs = []
+    for _ in range(3):
+        leg = {"sweep_ms": round(timed(lambda: plan.execute(stream), stream, args.warmup, args.steps), 4)}
+        for fmt in mx.FORMATS:
+            leg[fmt + "_ms"] = round(timed(lambda: calls[fmt].run(stream), stream, args.warmup, args.steps), 4)
+        legs.append(leg)
+    frac = lambda nbytes, ms: round(nbytes / ms / 1e6 / bench.HBM_PEAK_GBS, 4)   # noqa: E731
+    sweep_ms = statistics.median(leg["sweep_ms"] for leg in legs)
+    out = {"what": "dfq_mx_quantize_batch (dst + codes + scales + esum) on the bench headline list, beside the sweep",
+           "device": torch.cuda.get_device_name(dev), "model": b.model, "copies": copies, "tensors": len(items),
+           "elements": per_copy * copies, "warmup": args.warmup, "steps": args.steps, "legs": legs,
+           "sweep": {"bits": b.bits, "granularity": b.granularity, "symmetric": symmetric, "ms": sweep_ms,
+                     "algo_bytes": plan.stats["algo_bytes"], "launches": plan.stats["launches"],
+                     "frac_of_peak": frac(plan.stats["algo_bytes"], sweep_ms),
+                     "one_model_us": round(1e3 * timed(lambda: one_plan.execute(stream), stream, args.warmup,
+                                                       args.steps), 2)}}
+    for fmt in mx.FORMATS:
+        ms = statistics.median(leg[fmt + "_ms"] for leg in legs)
+        c = calls[fmt]
+        out[fmt] = {"ms": ms, "algo_bytes": c.algo_bytes, "frac_of_peak": frac(c.algo_bytes, ms),
+                    "bytes_per_element": round(c.algo_bytes / (per_copy * copies), 4),
+                    "ratio_to_sweep_ms": round(ms / sweep_ms, 3), "table_bytes": c.ws_bytes,
+                    "one_model_us": round(1e3 * timed(lambda: ones[fmt].run(stream), stream, args.warmup, args.steps), 2)}
+    torch.cuda.synchronize()
+    emit([out], Path(args.out) if args.out else OUT / "mx_quantize_time.jsonl")
+
+
+def quality_records(args):
+    """Model SQNR of the zoo's MobileNetV2 (seed 0) from main_dfq --relu [--equalize
+    --absorption] --quantize --report: both MX formats beside per-channel symmetric
+    INT4 / INT8, with and without equalization.  One JSON line each: data, not
+    assertions."""
+    import tempfile
+    from data_free_quantization_amd import main_dfq
+    records = []
+    with tempfile.TemporaryDirectory() as tmp:
+        for equalize in (True, False):
+            for fmt, extra in (("mxfp4", []), ("mxfp8", []),
+                               ("int", ["--bits_weight", "4", "--granularity", "channel", "--symmetric"]),
+                               ("int", ["--bits_weight", "8", "--granularity", "channel", "--symmetric"])):
+                path = Path(tmp) / "report.json"
+                argv = ["--relu"] + (["--equalize", "--absorption"] if equalize else []) + \
+                    ["--quantize", "--weight_format", fmt, "--report", str(path)] + extra
+                main_dfq.main(argv)
+                rep = json.loads(path.read_text())
+                m, cfg = rep["model"], rep["config"]
+                records.append({"argv": " ".join(argv[:-2 - len(extra)] + extra), "weight_format": fmt,
+                                "bits_per_weight": cfg.get("bits_per_weight", cfg["bits_weight"]), "equalize": equalize,
+                                "model_sqnr_db": round(m["sqnr_db"], 3), "worst_layer": m["worst_layer"],
+                                "worst_channel_sqnr_db": round(min(e["worst_channel_sqnr_db"] for e in rep["layers"]), 3)})
+    emit(records, Path(args.out) if args.out else OUT / "quality_mx.jsonl")
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--copies", type=int, default=0, help="weight sets (0: the bench's, >= 2 GiB)")
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--quality", action="store_true")
+    ap.add_argument("--out", default=None, help="the JSON lines' file (default: under profiles/r09)")
+    a = ap.parse_args()
+    quality_records(a) if a.quality else timing(a)
