@@ -46,6 +46,7 @@ DFQ_HOST_DEVICE inline int aten_ceil_log2(int64_t x) {
     return r;
 }
 
+constexpr int kWave = 64;   // gfx950 wave size: the kernels' and every planner's
 constexpr int kThreads = 256;
 constexpr int kColTileRows = 16;   // W2 rows per column tile (range and rescale tiles)
 

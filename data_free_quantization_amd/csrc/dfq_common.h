@@ -8,11 +8,9 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "dfq_hip.h"
-#include "dfq_cle_plan.h"   // ceil_div, aten_ceil_log2, ab_env: shared with the host-only planner
+#include "dfq_cle_plan.h"   // kWave, ceil_div, aten_ceil_log2, ab_env: shared with the host-only planners
 
 namespace dfq {
-
-constexpr int kWave = 64;
 
 // Ordered-uint encoding of fp32: enc is monotone in the float order (with -0 < +0),
 // so integer atomicMin/atomicMax give exact, order-independent float min/max.

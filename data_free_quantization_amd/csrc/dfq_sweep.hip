@@ -23,6 +23,7 @@
 // per-row reductions and the KHW error sums, and writes dq (16 B/lane), codes
 // (4 B/lane) and E.  Waves walk the task table grid-stride (persistent grid).
 #include "dfq_common.h"
+#include "dfq_sweep_plan.h"   // Variant, DevTensor, DevTask, the planner (host-only C++)
 #ifdef DFQ_DIAGNOSTICS
 #include "dfq_diag.h"
 #endif
@@ -31,101 +32,13 @@
 #include <cstring>
 #include <cstdlib>
 #include <new>
-#include <numeric>
 #include <type_traits>
 #include <vector>
 
 namespace dfq {
 
-constexpr int kWavesPerBlock = 4;
 constexpr int kBlockThreads = kWave * kWavesPerBlock;
 
-// Kernel variants (chunk elements per wave task, rows per whole-row task, LDS-DMA
-// prefetch of the next task).  The task table is built for the plan's variant.
-struct Variant {
-    int chunk;
-    int max_rows;
-    bool prefetch;
-};
-// max_rows: rows of one whole-row task; the host caps rows per task at
-// max(64 (one short row per lane), chunk / 32) (build()), so the per-row
-// parameter arrays (scale, min) take 2 * max_rows floats per wave.
-constexpr Variant kVariants[] = {
-    {2048, 64, false},    // 0: 8.5 KB LDS / wave, 16 waves / CU
-    {1024, 64, true},     // 1: 2 x 4 KB, next task's DMA in flight during compute
-    {2048, 64, true},     // 2: 2 x 8 KB
-    {1024, 64, false},    // 3: 4.5 KB / wave
-    {4096, 128, false},   // 4: 17 KB / wave, 8 waves / CU
-    {2048, 64, false},    // 5: variant 0 with non-temporal loads and stores
-    {2048, 64, false},    // 6: variant 5, KH*KW sums specialised for 3x3 only (fewer VGPRs)
-    {2048, 64, false},    // 7: variant 5, generic KH*KW sums only
-    {2560, 80, false},    // 8: variant 6 with 2560-element tasks (12 waves / CU)
-    {1024, 64, false},    // 9: variant 6 with 1024-element tasks
-    {1536, 64, false},    // 10: variant 6 with 1536-element tasks
-    {1024, 64, true},     // 11: 1024-element tasks, next task's DMA in flight, NT
-    {1024, 64, false},    // 12: variant 9 with the generic E sums (fewer VGPRs)
-    {2048, 64, false},    // 13: variant 6 + per-task timestamps (diagnostics: dfq_debug_timeline)
-    {2048, 64, false},    // 14: variant 6 with the IEEE divide on every element (round-2 arithmetic)
-    {2048, 64, false},    // 15: variant 6 with the generic quantize loop (flags tested per float4; round 3)
-    {2048, 64, false},    // 16: variant 6 with whole-row tasks in two row batches (compute_task_split)
-};
-constexpr int kNumVariants = 17;
-// HostTask / DevTask .nrows <= kGroupTag: a row-group piece of R = kGroupTag - nrows + 1 rows
-constexpr int kGroupTag = -64;
-constexpr int kGroupMaxRows = 16;
-#ifndef DFQ_DEFAULT_VARIANT   // compile-time override for side-by-side A/B builds (scripts/ab_variant_libs.py)
-#define DFQ_DEFAULT_VARIANT 6
-#endif
-constexpr int kDefaultVariant = DFQ_DEFAULT_VARIANT;   // 6 = 5 with 87 instead of 105 VGPRs (profiles/r01/ab_*_v568.json)
-
-struct alignas(16) DevTensor {
-    const float* src;
-    float* dst;
-    void* codes;
-    float* scale;
-    float* zero;
-    float* esum;
-    int64_t rows;
-    int64_t row_len;
-    int32_t khw;
-    int32_t bits;
-    int32_t mode;
-    int32_t flags;
-    float clip_lo;
-    float clip_hi;
-    double given_min;
-    double given_max;
-    float inv_len;     // 1/row_len, for the element -> row map inside a task
-    int32_t vec4;      // 16-B loads / stores legal
-    int32_t code_bytes;
-    uint32_t len_magic;  // ceil(2^32 / row_len): element -> row as one v_mul_hi_u32 (row_len >= 2)
-    const uint32_t* range_enc;   // DFQ_DEVICE_RANGE
-};
-
-// A wave task as the host builds it (HostTask) and as the kernels read it
-// (DevTask): the device record carries the address of its first element and the
-// tensor's 16-B-vector flag, so a wave issues the task's LDS-DMA as soon as the
-// record has landed, while the tensor's 128-B descriptor is still on its way
-// (one dependent scalar round trip off every task's critical path).
-struct HostTask {
-    int64_t elem_start;  // first element (tensor-relative)
-    int32_t tensor;
-    int32_t n;           // elements in the task
-    int32_t row0;        // first row of a whole-row task / the row of a long-row piece
-    int32_t nrows;       // > 0: whole rows; 0: slot piece; -1/-2/-4: block-row piece; <= kGroupTag: row group
-    int32_t slot;        // workspace (min,max) slot for pieces, -1 = given range
-    int32_t first;       // this piece writes scale/zero for its slot
-};
-struct alignas(16) DevTask {
-    const float* src;    // T.src + elem_start
-    int32_t tensor;
-    int32_t n;
-    int32_t row0;
-    int32_t nrows;
-    int32_t slot;
-    int32_t flags;       // bit 0: first (as HostTask); bit 1: T.vec4
-};
-static_assert(sizeof(DevTask) == 32, "one 32-B scalar load per task record");
 __device__ __forceinline__ int64_t task_elem_start(const DevTask& k, const DevTensor& T) { return k.src - T.src; }
 
 // Per-wave LDS image: [NB buffers of CHUNK floats][MAXROWS scales][MAXROWS mins]
@@ -1080,304 +993,8 @@ sweep_main_kernel(const DevTensor* __restrict__ tensors, const DevTask* __restri
 }
 
 // ---------------------------------------------------------------------------
-// Host: validation, task building, plans.
+// Host: kernel selection, plans (the planner itself: dfq_sweep_plan.cpp).
 // ---------------------------------------------------------------------------
-static bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
-static int validate(const dfq_tensor_desc& d) {
-    if (d.rows < 0 || d.row_len < 0) return DFQ_ERR_INVALID;
-    if (!d.src && d.rows * d.row_len > 0) return DFQ_ERR_INVALID;
-    if (d.bits < 2 || d.bits > 16) return DFQ_ERR_INVALID;
-    if (d.mode < DFQ_TENSOR_ASYM || d.mode > DFQ_CHANNEL_SYM) return DFQ_ERR_INVALID;
-    if (d.khw < 1) return DFQ_ERR_INVALID;
-    if (d.esum && (d.row_len % d.khw) != 0) return DFQ_ERR_SHAPE;
-    if (d.rows > INT32_MAX) return DFQ_ERR_UNSUPPORTED;
-    const bool channel = d.mode >= DFQ_CHANNEL_ASYM;
-    if (channel && (d.flags & DFQ_GIVEN_RANGE)) return DFQ_ERR_INVALID;
-    if (d.flags & DFQ_DEVICE_RANGE) {
-        if (channel || (d.flags & DFQ_GIVEN_RANGE) || !d.range_enc) return DFQ_ERR_INVALID;
-    }
-    return DFQ_OK;
-}
-
-struct Built {
-    std::vector<DevTensor> tensors;
-    std::vector<HostTask> reduce;
-    std::vector<HostTask> blockrow;   // groups of kWavesPerBlock, placed first in the main list
-    std::vector<HostTask> main;       // block rows, then tasks needing no reduce, then slot pieces
-    std::vector<HostTask> slotted;    // slot pieces, in reduce order (appended to main at the end)
-    int64_t slots = 0;
-    int64_t elems = 0;
-    int64_t algo_bytes = 0;
-};
-
-static DevTensor to_dev(const dfq_tensor_desc& d) {
-    DevTensor t{};
-    t.src = d.src; t.dst = d.dst; t.codes = d.codes; t.scale = d.scale; t.zero = d.zero; t.esum = d.esum;
-    t.rows = d.rows; t.row_len = d.row_len; t.khw = d.khw; t.bits = d.bits; t.mode = d.mode;
-    t.flags = d.flags; t.clip_lo = d.clip_lo; t.clip_hi = d.clip_hi;
-    t.given_min = d.given_min; t.given_max = d.given_max;
-    t.range_enc = (d.flags & DFQ_DEVICE_RANGE) ? d.range_enc : nullptr;
-    t.inv_len = d.row_len > 0 ? 1.0f / (float)d.row_len : 0.f;
-    t.len_magic = (d.row_len >= 2 && d.row_len < (int64_t(1) << 31))
-                      ? (uint32_t)(((uint64_t(1) << 32) + (uint64_t)d.row_len - 1) / (uint64_t)d.row_len)
-                      : 0u;
-    t.code_bytes = (d.flags & DFQ_PACK_INT4) ? 0 : (d.bits <= 8 ? 1 : 2);   // 0: packed nibbles
-    const int64_t n = d.rows * d.row_len;
-    const bool channel = d.mode >= DFQ_CHANNEL_ASYM;
-    bool v = (n % 4 == 0) && aligned(d.src, 16) && (!d.dst || aligned(d.dst, 16)) &&
-             (!d.codes || aligned(d.codes, t.code_bytes ? 4 * t.code_bytes : 2)) &&
-             (!d.esum || d.khw > 1 || aligned(d.esum, 16));
-    if (channel) v = v && (d.row_len % 4 == 0);
-    t.vec4 = v ? 1 : 0;
-    return t;
-}
-
-// Piece length: a multiple of khw (E sums never straddle a piece), of 4 (vec4)
-// and of 2 (packed nibbles: a byte never straddles two tasks).
-static int piece_len(int khw, bool vec4, int chunk, bool packed = false) {
-    const int unit = vec4 ? std::lcm(4, khw) : (packed ? std::lcm(2, khw) : khw);
-    int p = (chunk / unit) * unit;
-    return p > 0 ? p : -1;
-}
-
-// A/B and diagnostics switches (DFQ_SWEEP_VARIANT / _REDUCE_SPAN /
-// _SHUFFLE / _BLOCKS_PER_CU) are read only by the diagnostics library
-// (libdfq_diag.so, -DDFQ_DIAGNOSTICS); the product library runs the measured
-// defaults whatever the environment says.
-
-// DFQ_SWEEP_GROUP_ROWS=1 (diagnostics): per-channel rows of kChunk/2 .. 4 kChunk
-// elements as row groups instead of whole-row tasks / block-row pieces.  Bit-exact
-// and neutral (-1.4 .. +1.4 % on the five replicated configs interleaved on one box,
-// profiles/r02/ab_group_rows.json: task fill is not what limits the 3x3 families),
-// so the product keeps the simpler tasks.
-static bool group_rows_enabled() {
-    const char* e = ab_env("DFQ_SWEEP_GROUP_ROWS");
-    return e && e[0] == '1';
-}
-
-// DFQ_SWEEP_BLOCKROW=0 (diagnostics library): long rows through the reduce launch
-// instead (an alternative schedule, parity-tested against the default).
-static bool blockrow_enabled() {
-    const char* e = ab_env("DFQ_SWEEP_BLOCKROW");
-    return !(e && e[0] == '0');
-}
-
-// Two-pass ranges pipelined in slabs (the quantize pass of slab k re-reading its
-// inputs while they are still in the 256 MB Infinity Cache, on two streams) were
-// measured slower at every slab size (profiles/r02/ab_slab.json: 16-256 MB slabs
-// 1.34-3.9 ms per step against 1.11 for the two passes back to back) and deleted
-// in round 4.
-
-// Reduce-launch tasks: consecutive pieces of one range merged up to `span`
-// elements per wave task (fewer same-address atomics, longer read streams).
-// DFQ_SWEEP_REDUCE_SPAN overrides (A/B).
-static int64_t reduce_span() {
-    const char* e = ab_env("DFQ_SWEEP_REDUCE_SPAN");
-    return (e && *e) ? std::max<int64_t>(1, atoll(e)) : 16384;
-}
-static void push_reduce(std::vector<HostTask>& R, const HostTask& k, int64_t span) {
-    if (!R.empty()) {
-        HostTask& p = R.back();
-        if (p.slot == k.slot && p.tensor == k.tensor && p.elem_start + p.n == k.elem_start &&
-            (int64_t)p.n + k.n <= span) {
-            p.n += k.n;
-            return;
-        }
-    }
-    R.push_back(k);
-}
-
-// DFQ_SWEEP_SHUFFLE=<seed> (A/B): visit the main list's 4-task units (one
-// workgroup's grid-stride step; block-row groups stay whole) in a seeded random
-// order instead of list order.
-static void shuffle_quads(Built& B) {
-    const char* e = ab_env("DFQ_SWEEP_SHUFFLE");
-    if (!e || !*e) return;
-    const int64_t units = (int64_t)B.main.size() / kWavesPerBlock;
-    if (units < 2) return;
-    uint64_t x = (uint64_t)atoll(e) * 0x9E3779B97F4A7C15ull + 1;
-    auto next = [&x]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; };
-    for (int64_t u = units - 1; u > 0; --u) {
-        const int64_t v = (int64_t)(next() % (uint64_t)(u + 1));
-        if (v != u)
-            std::swap_ranges(B.main.begin() + u * kWavesPerBlock, B.main.begin() + (u + 1) * kWavesPerBlock,
-                             B.main.begin() + v * kWavesPerBlock);
-    }
-}
-
-static int build(const dfq_tensor_desc* descs, int32_t n, Built& B, const Variant& V) {
-    const int64_t rspan = reduce_span();
-    const bool use_blockrow = blockrow_enabled();
-    const int kChunk = V.chunk, kMaxRows = V.max_rows;
-    for (int32_t ti = 0; ti < n; ++ti) {
-        const dfq_tensor_desc& d = descs[ti];
-        int rc = validate(d);
-        if (rc) return rc;
-        DevTensor T = to_dev(d);
-        const bool packed = (d.flags & DFQ_PACK_INT4) != 0;
-        if (packed && d.bits > 4) return DFQ_ERR_INVALID;
-        // packed codes need every task to start at an even element: per channel,
-        // odd rows must come in pairs within one whole-row task (row_len <= chunk/2)
-        if (packed && d.mode >= DFQ_CHANNEL_ASYM && (d.row_len & 1) && 2 * d.row_len > kChunk &&
-            d.rows > 1)
-            return DFQ_ERR_UNSUPPORTED;
-        const int64_t total = d.rows * d.row_len;
-        B.elems += total;
-        // algorithmic bytes: read x, write dq / codes / E / per-row params once
-        int64_t bytes = 4 * total;
-        if (d.dst) bytes += 4 * total;
-        if (d.codes) bytes += T.code_bytes ? (int64_t)T.code_bytes * total : total / 2;
-        if (d.esum) bytes += 4 * (total / d.khw);
-        const bool channel = d.mode >= DFQ_CHANNEL_ASYM;
-        const int64_t nparams = channel ? d.rows : 1;
-        if (d.scale) bytes += 4 * nparams;
-        if (d.zero) bytes += 4 * nparams;
-        B.algo_bytes += bytes;
-        B.tensors.push_back(T);
-        if (total == 0) continue;
-        const int plen = piece_len(d.khw, T.vec4, kChunk, packed);
-        if (plen <= 0) return DFQ_ERR_UNSUPPORTED;   // khw > kChunk
-        // a given or device-resident range: single-pass tasks, no slot
-        const bool given = (d.flags & (DFQ_GIVEN_RANGE | DFQ_DEVICE_RANGE)) != 0;
-        const int64_t blen = channel ? d.row_len : total;   // the range's extent
-        // Row groups (per-channel rows of kChunk/2 .. 4 kChunk elements): R whole rows
-        // split into 4 balanced pieces, one per wave of a block, the rows' ranges
-        // combined through LDS -- tasks hold ~R len / 4 elements instead of one row
-        // (1,152-element 3x3 rows: 56 % of a task) or half a row.
-        int64_t grp_rows = 0, grp_unit = 0;
-        if (channel && use_blockrow && !V.prefetch && !given && d.row_len > kChunk / 2 &&
-            d.row_len <= (int64_t)kWavesPerBlock * kChunk && group_rows_enabled()) {
-            grp_unit = T.vec4 ? std::lcm<int64_t>(4, d.khw) : (packed ? std::lcm<int64_t>(2, d.khw) : d.khw);
-            for (int64_t R = std::min<int64_t>(kGroupMaxRows, (int64_t)kWavesPerBlock * kChunk / d.row_len); R >= 1;
-                 --R) {
-                const int64_t piece = ceil_div(ceil_div(R * d.row_len, grp_unit), (int64_t)kWavesPerBlock) * grp_unit;
-                if (piece <= kChunk) {
-                    grp_rows = R;
-                    break;
-                }
-            }
-            // whole-row tasks already fill >= 85 % of a task: keep them
-            if (grp_rows > 0 && d.row_len <= kChunk && (kChunk / d.row_len) * d.row_len * 100 >= 85 * kChunk)
-                grp_rows = 0;
-        }
-        if (grp_rows > 0) {
-            for (int64_t r0 = 0; r0 < d.rows; r0 += grp_rows) {
-                const int64_t R = std::min<int64_t>(grp_rows, d.rows - r0);
-                const int64_t tot = R * d.row_len;
-                const int64_t piece = ceil_div(ceil_div(tot, grp_unit), (int64_t)kWavesPerBlock) * grp_unit;
-                for (int i = 0; i < kWavesPerBlock; ++i) {
-                    const int64_t off = std::min<int64_t>((int64_t)i * piece, tot);
-                    HostTask k{};
-                    k.tensor = ti; k.slot = -1; k.first = 0;
-                    k.nrows = kGroupTag - (int32_t)(R - 1);
-                    k.row0 = (int32_t)r0;
-                    k.elem_start = r0 * d.row_len + off;
-                    k.n = (int32_t)std::min<int64_t>(piece, tot - off);
-                    B.blockrow.push_back(k);
-                }
-            }
-            continue;
-        }
-        const bool block_row = use_blockrow && !V.prefetch && !given && blen <= (int64_t)kWavesPerBlock * plen &&
-                               (!channel || d.row_len > kChunk);
-        if (block_row) {
-            // A group of 4 list entries = 4 waves of one block: one row in 4 pieces,
-            // or (rows <= 2 pieces) two rows in 2 pieces each.  Balanced pieces:
-            // the group waits for its slowest wave.
-            const int64_t nr = channel ? d.rows : 1;
-            const int gs = blen <= 2 * (int64_t)plen ? 2 : kWavesPerBlock;
-            const int64_t unit = T.vec4 ? std::lcm<int64_t>(4, d.khw) : (packed ? std::lcm<int64_t>(2, d.khw) : d.khw);
-            const int64_t bpl = ceil_div(ceil_div(blen, unit), (int64_t)gs) * unit;
-            const int64_t rows_per_group = kWavesPerBlock / gs;
-            for (int64_t r0 = 0; r0 < nr; r0 += rows_per_group) {
-                for (int i = 0; i < kWavesPerBlock; ++i) {
-                    const int64_t r = r0 + i / gs;
-                    const int64_t off = (int64_t)(i % gs) * bpl;
-                    HostTask k{};
-                    k.tensor = ti; k.nrows = -gs; k.slot = -1;
-                    if (r < nr) {
-                        k.elem_start = r * blen + std::min<int64_t>(off, blen);
-                        k.n = (int32_t)std::max<int64_t>(0, std::min<int64_t>(bpl, blen - off));
-                        k.row0 = (int32_t)r; k.first = (i % gs == 0);
-                    } else {   // padding half-group: no data, writes nothing
-                        k.elem_start = r0 * blen; k.n = 0; k.row0 = (int32_t)r0; k.first = 0;
-                    }
-                    B.blockrow.push_back(k);
-                }
-            }
-        } else if (channel && d.row_len <= kChunk) {
-            // short rows (depthwise 3x3: 9 elements) are reduced one lane per row and run
-            // the scalar path: at most one row per lane keeps such a task's latency
-            // near a vector task's (single-model sweeps are latency-bound)
-            const int64_t row_cap = d.row_len < 32 ? kWave : kMaxRows;
-            int64_t rpt = std::max<int64_t>(1, std::min<int64_t>(row_cap, kChunk / d.row_len));
-            if (packed && (d.row_len & 1) && rpt > 1) rpt &= ~int64_t(1);   // even task starts
-            for (int64_t r = 0; r < d.rows; r += rpt) {
-                const int64_t nr = std::min<int64_t>(rpt, d.rows - r);
-                HostTask k{};
-                k.elem_start = r * d.row_len; k.tensor = ti; k.n = (int32_t)(nr * d.row_len);
-                k.row0 = (int32_t)r; k.nrows = (int32_t)nr; k.slot = -1; k.first = 0;
-                B.main.push_back(k);
-            }
-        } else if (channel) {   // long rows: one slot per row
-            for (int64_t r = 0; r < d.rows; ++r) {
-                const int64_t slot = B.slots++;
-                for (int64_t off = 0; off < d.row_len; off += plen) {
-                    HostTask k{};
-                    k.elem_start = r * d.row_len + off; k.tensor = ti;
-                    k.n = (int32_t)std::min<int64_t>(plen, d.row_len - off);
-                    k.row0 = (int32_t)r; k.nrows = 0; k.slot = (int32_t)slot; k.first = (off == 0);
-                    push_reduce(B.reduce, k, rspan);
-                    B.slotted.push_back(k);
-                }
-            }
-        } else {                // tensor modes: one slot per tensor (none for a given range)
-            const int64_t slot = given ? -1 : B.slots++;
-            for (int64_t off = 0; off < total; off += plen) {
-                HostTask k{};
-                k.elem_start = off; k.tensor = ti; k.n = (int32_t)std::min<int64_t>(plen, total - off);
-                k.row0 = 0; k.nrows = 0; k.slot = (int32_t)slot; k.first = (off == 0);
-                if (!given) {
-                    push_reduce(B.reduce, k, rspan);
-                    B.slotted.push_back(k);
-                } else {
-                    B.main.push_back(k);
-                }
-            }
-        }
-    }
-    B.main.insert(B.main.begin(), B.blockrow.begin(), B.blockrow.end());
-    B.main.insert(B.main.end(), B.slotted.begin(), B.slotted.end());   // slot pieces after the single-pass tasks
-    shuffle_quads(B);
-    return DFQ_OK;
-}
-
-// The device form of a task list (DevTask: the first element's address, the
-// tensor's vector flag) into `out`.
-static void put_tasks(const std::vector<HostTask>& h, const std::vector<DevTensor>& T, char* out) {
-    DevTask* d = reinterpret_cast<DevTask*>(out);
-    for (size_t i = 0; i < h.size(); ++i) {
-        const HostTask& k = h[i];
-        const DevTensor& t = T[k.tensor];
-        d[i] = DevTask{t.src + k.elem_start, k.tensor, k.n, k.row0, k.nrows, k.slot,
-                       (k.first ? 1 : 0) | (t.vec4 ? 2 : 0)};
-    }
-}
-
-static int variant_from_env() {
-    const char* e = ab_env("DFQ_SWEEP_VARIANT");
-    if (!e || !*e) return kDefaultVariant;
-    const int v = atoi(e);
-    return (v >= 0 && v < kNumVariants) ? v : kDefaultVariant;
-}
-
-
-// Small lists (see build_planned) run variant 10's 1,536-element tasks; one round
-// of resident sweep blocks on the 256-CU part is 4 per CU.
-constexpr int kSmallVariant = 10;
-constexpr int64_t kResidentBlocks = 4 * 256;
-
 static int lds_bytes(const Variant& V) {
     return 4 * kWavesPerBlock * ((V.prefetch ? 2 : 1) * V.chunk + 3 * V.max_rows);
 }
@@ -1433,11 +1050,38 @@ static int grid_for(int64_t ntasks) {
     const int64_t want = ceil_div(ntasks, kWavesPerBlock);
     return (int)std::max<int64_t>(1, std::min<int64_t>(want, 256 * (int64_t)blocks_per_cu()));
 }
-static int grid_for_variant(int64_t ntasks, int) { return grid_for(ntasks); }
 
-static void launch_main(int variant, int grid, hipStream_t s, const DevTensor* t, const DevTask* k, int64_t n,
-                        const uint32_t* smin, const uint32_t* smax) {
-    hipLaunchKernelGGL(main_kernel(variant), dim3(grid), dim3(kBlockThreads), 0, s, t, k, n, smin, smax);
+// One run of a table on `s`: the slots armed (mins all ones, maxs zero) and one
+// reduce launch over every slot piece, if there are any, then one main launch.
+static int launch_sweep(int variant, hipStream_t s, const DevTensor* t, const DevTask* reduce, int64_t n_reduce,
+                        const DevTask* main, int64_t n_main, uint32_t* slots, int64_t n_slots) {
+    if (n_reduce > 0) {
+        DFQ_HIP_CHECK(hipMemsetAsync(slots, 0xFF, sizeof(uint32_t) * n_slots, s));
+        DFQ_HIP_CHECK(hipMemsetAsync(slots + n_slots, 0x00, sizeof(uint32_t) * n_slots, s));
+        hipLaunchKernelGGL(sweep_reduce_kernel, dim3(grid_for(n_reduce)), dim3(kBlockThreads), 0, s, t, reduce,
+                           n_reduce, slots, slots + n_slots);
+        DFQ_LAUNCH_CHECK();
+    }
+    if (n_main > 0) {
+        hipLaunchKernelGGL(main_kernel(variant), dim3(grid_for(n_main)), dim3(kBlockThreads), 0, s, t, main, n_main,
+                           slots, slots + n_slots);
+        DFQ_LAUNCH_CHECK();
+    }
+    return DFQ_OK;
+}
+
+// The host-built tables [tensors .. main tasks] as one blob for a single upload:
+// each part at its layout offset less the tensors' (the parts between stay zero).
+static std::vector<char> table_blob(const SweepTables& T, size_t o_tensors, size_t o_reduce, size_t o_main,
+                                    size_t end) {
+    std::vector<char> blob(end - o_tensors, 0);
+    auto put = [&](size_t off, const void* p, size_t bytes) {
+        if (bytes) std::memcpy(blob.data() + (off - o_tensors), p, bytes);
+    };
+    put(o_tensors, T.tensors.data(), sizeof(DevTensor) * T.tensors.size());
+    put(o_reduce, T.reduce.data(), sizeof(DevTask) * T.reduce.size());
+    put(o_main, T.main.data(), sizeof(DevTask) * T.main.size());
+    return blob;
 }
 
 }  // namespace dfq
@@ -1454,55 +1098,6 @@ struct dfq_sweep_plan {
     int64_t n_reduce = 0, n_main = 0, n_slots = 0, n_tensors = 0, n_elems = 0, algo_bytes = 0;
 };
 
-namespace dfq {
-// Device layout of a plan's tables: [tensors | reduce tasks | main tasks | slots],
-// each 256-B aligned (one allocation or one caller workspace).
-struct PlanLayout {
-    int64_t o_tensors = 0, o_reduce = 0, o_main = 0, o_slots = 0, total = 0;
-};
-static int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
-static PlanLayout plan_layout(const Built& B, int64_t n) {
-    PlanLayout L;
-    L.o_tensors = 0;
-    L.o_reduce = L.o_tensors + align256((int64_t)sizeof(DevTensor) * n);
-    L.o_main = L.o_reduce + align256((int64_t)sizeof(DevTask) * (int64_t)B.reduce.size());
-    L.o_slots = L.o_main + align256((int64_t)sizeof(DevTask) * (int64_t)B.main.size());
-    L.total = L.o_slots + align256((int64_t)sizeof(uint32_t) * 2 * B.slots);
-    return L;
-}
-}  // namespace dfq
-
-// The plan's kernel variant and task table.  A diagnostics DFQ_SWEEP_VARIANT wins.
-// Otherwise the default variant's 2,048-element tasks, unless the list is small
-// enough that 1,536-element tasks (variant 10) still fit in ONE round of resident
-// blocks (4 per CU at 97 VGPRs): a one-round grid of range-dependent tasks is
-// latency-bound, and 4/3 as many waves hide more of it (MobileNetV2 single model:
-// 560 -> 747 blocks).  Lists past one round keep 2,048 (DeepLab's single model at
-// 1,536 needs 1,123 blocks and measured 12.0 against 9.2 us; profiles/r06/chunk_rule_ab_r06o.jsonl).
-static int build_planned(const dfq_tensor_desc* descs, int32_t n, Built& B, int& variant) {
-    const char* e = ab_env("DFQ_SWEEP_VARIANT");
-    variant = variant_from_env();
-    if (int rc = build(descs, n, B, kVariants[variant])) return rc;
-    if ((e && *e) || variant != kDefaultVariant || kDefaultVariant != 6) return DFQ_OK;
-    const int64_t limit = kResidentBlocks;
-    const int64_t blocks = ceil_div((int64_t)B.main.size(), (int64_t)kWavesPerBlock);
-    if (B.main.empty() || 4 * blocks > 3 * limit) return DFQ_OK;   // 4/3 the tasks would not fit one round
-    Built S;
-    if (build(descs, n, S, kVariants[kSmallVariant]) != DFQ_OK) return DFQ_OK;
-    if (ceil_div((int64_t)S.main.size(), (int64_t)kWavesPerBlock) > limit) return DFQ_OK;
-    B = std::move(S);
-    variant = kSmallVariant;
-    return DFQ_OK;
-}
-
-extern "C" int64_t dfq_sweep_plan_ws_bytes(const dfq_tensor_desc* descs, int32_t n) {
-    if ((n > 0 && !descs) || n < 0) return -1;
-    Built B;
-    int variant = 0;
-    if (build_planned(descs, n, B, variant)) return -1;
-    return plan_layout(B, n).total;
-}
-
 // ws == NULL: the plan owns one hipMalloc'ed table block (blocking copy).  Else the
 // tables go to the caller's stream-ordered workspace: one copy on `stream`, then a
 // sync of that stream (the host staging dies with the call).
@@ -1510,15 +1105,14 @@ static int sweep_plan_create_impl(const dfq_tensor_desc* descs, int32_t n, void*
                                   hipStream_t stream, dfq_sweep_plan** out) {
     if (!out || (n > 0 && !descs) || n < 0) return DFQ_ERR_INVALID;
     *out = nullptr;
-    int variant = 0;
-    Built B;
-    int rc = build_planned(descs, n, B, variant);
+    SweepTables B;
+    PlanLayout Lo;
+    int rc = sweep_plan_tables(descs, n, B, Lo);
     if (rc) return rc;
-    const PlanLayout Lo = plan_layout(B, n);
     if (ws && (ws_bytes < Lo.total || reinterpret_cast<uintptr_t>(ws) % 256 != 0)) return DFQ_ERR_WORKSPACE;
     dfq_sweep_plan* p = new (std::nothrow) dfq_sweep_plan();
     if (!p) return DFQ_ERR_NOMEM;
-    p->variant = variant;
+    p->variant = B.variant;
     p->n_reduce = (int64_t)B.reduce.size();
     p->n_main = (int64_t)B.main.size();
     p->n_slots = B.slots;
@@ -1536,10 +1130,7 @@ static int sweep_plan_create_impl(const dfq_tensor_desc* descs, int32_t n, void*
     p->d_main = reinterpret_cast<DevTask*>(base + Lo.o_main);
     p->d_slots = reinterpret_cast<uint32_t*>(base + Lo.o_slots);
     if (e == hipSuccess) {
-        std::vector<char> blob(Lo.o_slots, 0);   // the host-built tables
-        if (n > 0) std::memcpy(blob.data() + Lo.o_tensors, B.tensors.data(), sizeof(DevTensor) * n);
-        put_tasks(B.reduce, B.tensors, blob.data() + Lo.o_reduce);
-        put_tasks(B.main, B.tensors, blob.data() + Lo.o_main);
+        const std::vector<char> blob = table_blob(B, Lo.o_tensors, Lo.o_reduce, Lo.o_main, Lo.o_slots);
         if (ws) {   // stream-ordered: pinned staging, no host synchronisation
             e = stage_h2d(base, blob.data(), Lo.o_slots, stream);
         } else {
@@ -1568,23 +1159,8 @@ extern "C" int dfq_sweep_plan_create_ws(const dfq_tensor_desc* descs, int32_t n,
 
 extern "C" int dfq_sweep_plan_execute(dfq_sweep_plan* p, void* stream) {
     if (!p) return DFQ_ERR_INVALID;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (p->n_reduce > 0) {
-        DFQ_HIP_CHECK(hipMemsetAsync(p->d_slots, 0xFF, sizeof(uint32_t) * p->n_slots, s));
-        DFQ_HIP_CHECK(hipMemsetAsync(p->d_slots + p->n_slots, 0x00, sizeof(uint32_t) * p->n_slots, s));
-    }
-    // one reduce launch over every slot piece, then one main launch
-    if (p->n_reduce > 0) {
-        hipLaunchKernelGGL(sweep_reduce_kernel, dim3(grid_for(p->n_reduce)), dim3(kBlockThreads), 0, s, p->d_tensors,
-                           p->d_reduce, p->n_reduce, p->d_slots, p->d_slots + p->n_slots);
-        DFQ_LAUNCH_CHECK();
-    }
-    if (p->n_main > 0) {
-        launch_main(p->variant, grid_for_variant(p->n_main, p->variant), s, p->d_tensors, p->d_main, p->n_main,
-                    p->d_slots, p->d_slots + p->n_slots);
-        DFQ_LAUNCH_CHECK();
-    }
-    return DFQ_OK;
+    return launch_sweep(p->variant, static_cast<hipStream_t>(stream), p->d_tensors, p->d_reduce, p->n_reduce, p->d_main,
+                        p->n_main, p->d_slots, p->n_slots);
 }
 
 extern "C" int dfq_sweep_plan_stats(const dfq_sweep_plan* p, dfq_sweep_stats* st) {
@@ -1595,7 +1171,7 @@ extern "C" int dfq_sweep_plan_stats(const dfq_sweep_plan* p, dfq_sweep_stats* st
     st->n_tasks_main = p->n_main;
     st->algo_bytes = p->algo_bytes;
     st->launches = (p->n_reduce > 0 ? 1 : 0) + (p->n_main > 0 ? 1 : 0);
-    st->grid_blocks = p->n_main > 0 ? grid_for_variant(p->n_main, p->variant) : 0;
+    st->grid_blocks = p->n_main > 0 ? grid_for(p->n_main) : 0;
     st->variant = p->variant;
     return DFQ_OK;
 }
@@ -1612,68 +1188,23 @@ extern "C" int dfq_sweep_plan_destroy(dfq_sweep_plan* p) {
 // tables go up through the pinned staging ring (stage_h2d), so a call is
 // asynchronous on the caller's stream like every other entry point.
 // ---------------------------------------------------------------------------
-namespace dfq {
-static size_t single_ws_layout(const Built& B, size_t* off_tensor, size_t* off_reduce, size_t* off_main) {
-    size_t o = 0;
-    o += sizeof(uint32_t) * 2 * (size_t)B.slots;
-    o = (o + 63) & ~size_t(63);
-    *off_tensor = o; o += sizeof(DevTensor) * B.tensors.size();
-    o = (o + 63) & ~size_t(63);
-    *off_reduce = o; o += sizeof(DevTask) * B.reduce.size();
-    o = (o + 63) & ~size_t(63);
-    *off_main = o; o += sizeof(DevTask) * B.main.size();
-    return o;
-}
-}  // namespace dfq
-
-extern "C" int dfq_quantize_ws_bytes(const dfq_tensor_desc* d, size_t* bytes) {
-    if (!d || !bytes) return DFQ_ERR_INVALID;
-    Built B;
-    int rc = build(d, 1, B, kVariants[kDefaultVariant]);
-    if (rc) return rc;
-    size_t a, b, c;
-    *bytes = single_ws_layout(B, &a, &b, &c);
-    return DFQ_OK;
-}
-
 extern "C" int dfq_quantize_tensor(const dfq_tensor_desc* d, void* ws, size_t ws_bytes, void* stream) {
     if (!d) return DFQ_ERR_INVALID;
-    Built B;
-    int rc = build(d, 1, B, kVariants[kDefaultVariant]);
+    SweepTables B;
+    SingleLayout Lo;
+    int rc = sweep_single_tables(*d, B, Lo);
     if (rc) return rc;
-    size_t ot, orr, om;
-    const size_t need = single_ws_layout(B, &ot, &orr, &om);
-    if (!ws || ws_bytes < need) return DFQ_ERR_WORKSPACE;
+    if (!ws || ws_bytes < Lo.total) return DFQ_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     char* base = static_cast<char*>(ws);
-    uint32_t* slots = reinterpret_cast<uint32_t*>(base);
-    DevTensor* dt = reinterpret_cast<DevTensor*>(base + ot);
-    DevTask* dr = reinterpret_cast<DevTask*>(base + orr);
-    DevTask* dm = reinterpret_cast<DevTask*>(base + om);
+    DevTensor* dt = reinterpret_cast<DevTensor*>(base + Lo.o_tensor);
     // one table blob [tensor | reduce tasks | main tasks] through the pinned staging
     // ring: stream-ordered, no host synchronisation
-    {
-        const size_t tb = om + sizeof(DevTask) * B.main.size() - ot;
-        std::vector<char> blob(tb, 0);
-        std::memcpy(blob.data(), B.tensors.data(), sizeof(DevTensor));
-        put_tasks(B.reduce, B.tensors, blob.data() + (orr - ot));
-        put_tasks(B.main, B.tensors, blob.data() + (om - ot));
-        DFQ_HIP_CHECK(stage_h2d(dt, blob.data(), tb, s));
-    }
-    if (!B.reduce.empty()) {
-        DFQ_HIP_CHECK(hipMemsetAsync(slots, 0xFF, sizeof(uint32_t) * B.slots, s));
-        DFQ_HIP_CHECK(hipMemsetAsync(slots + B.slots, 0x00, sizeof(uint32_t) * B.slots, s));
-        hipLaunchKernelGGL(sweep_reduce_kernel, dim3(grid_for((int64_t)B.reduce.size())), dim3(kBlockThreads), 0, s,
-                           dt, dr, (int64_t)B.reduce.size(), slots, slots + B.slots);
-        DFQ_LAUNCH_CHECK();
-    }
-    if (!B.main.empty()) {
-        launch_main(kDefaultVariant, grid_for_variant((int64_t)B.main.size(), kDefaultVariant), s, dt, dm,
-                    (int64_t)B.main.size(), slots,
-                    slots + B.slots);
-        DFQ_LAUNCH_CHECK();
-    }
-    return DFQ_OK;
+    const std::vector<char> blob = table_blob(B, Lo.o_tensor, Lo.o_reduce, Lo.o_main, Lo.total);
+    DFQ_HIP_CHECK(stage_h2d(dt, blob.data(), blob.size(), s));
+    return launch_sweep(B.variant, s, dt, reinterpret_cast<DevTask*>(base + Lo.o_reduce), (int64_t)B.reduce.size(),
+                        reinterpret_cast<DevTask*>(base + Lo.o_main), (int64_t)B.main.size(),
+                        reinterpret_cast<uint32_t*>(base), B.slots);
 }
 
 #ifdef DFQ_DIAGNOSTICS

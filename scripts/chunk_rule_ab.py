@@ -1,7 +1,7 @@
 """Task size against list size: variant 6 (2,048-element tasks) vs 10 (1,536) over
 lists of 1..64 weight sets, device us per execute from HIP-graph replays, both
-variants alternated twice in the same process.  Evidence for build_planned's rule
-(csrc/dfq_sweep.hip).  usage: python scripts/chunk_rule_ab.py  (diagnostics library)"""
+variants alternated twice in the same process.  Evidence for sweep_plan_tables' rule
+(csrc/dfq_sweep_plan.cpp).  usage: python scripts/chunk_rule_ab.py  (diagnostics library)"""
 import os
 os.environ.setdefault("DFQ_LIB", "diag")
 import json
