@@ -125,6 +125,7 @@ DFQ_PAIR_PIECE_ELEMS = 8192
 DFQ_CLIP_PIECE_ELEMS, DFQ_CLIP_MAX_CANDIDATES, DFQ_CLIP_SEARCH_DRY = 4096, 64, 1
 DFQ_MX_BLOCK = 32
 DFQ_MX_FP4_E2M1, DFQ_MX_FP8_E4M3 = 0, 1
+DFQ_MX_FP6_E2M3, DFQ_MX_FP6_E3M2 = 0x23, 0x32   # self-describing (exponent, mantissa bits): 2 stays invalid
 DFQ_MX_TASK_ELEMS, DFQ_MX_ESUM_TASK_ELEMS = 4096, 2048
 
 _LIB: Optional[C.CDLL] = None

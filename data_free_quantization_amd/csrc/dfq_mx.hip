@@ -7,10 +7,12 @@
 // lane, so eight neighbouring lanes hold one MX block: the block's amax is a maximum
 // over those eight lanes (DPP, on the magnitudes' bit patterns: integer compares,
 // no NaN rule, no canonicalisation), each lane converts its four elements and stores
-// 16 B of dst, 2 B of packed FP4 or 4 B of FP8, and the block's first lane its scale
-// byte -- all of them consecutive across the wave.  Codes and scales are addressed by
-// v alone ([rows, nb, 16 | 32] and [rows, nb] are the padded numbering), so the
-// padding of a partial block is written as +0 codes by the lanes that hold it.
+// 16 B of dst, 2 B of packed FP4, 3 B of packed FP6 or 4 B of FP8, and the block's
+// first lane its scale byte -- all of them consecutive across the wave.  Codes and
+// scales are addressed by v alone ([rows, nb, 16 | 24 | 32] and [rows, nb] are the
+// padded numbering), so the padding of a partial block is written as +0 codes by the
+// lanes that hold it.  (FP6: a lane's four codes are 24 bits; on the 16-B path a quad
+// of lanes regroups its 12 bytes into three dword stores, mx_task.)
 // Rows that do not start 16-B aligned take the same walk with 4-B accesses.
 // The conversion is plain integer / fp32 arithmetic (mx_encode): exact power-of-two
 // scalings, one round-to-nearest-even (v_rndne_f32) and a saturating integer min.
@@ -38,11 +40,25 @@ struct MxFmt;
 template <>
 struct MxFmt<DFQ_MX_FP4_E2M1> {
     static constexpr int mbits = 1, emin = 0, emax = 2, max_code = 0x7, sign = 0x8;
+    static constexpr float qmax = 6.0f;   // the magnitude of max_code
 };
 template <>
 struct MxFmt<DFQ_MX_FP8_E4M3> {
     static constexpr int mbits = 3, emin = -6, emax = 8, max_code = 0x7E, sign = 0x80;   // 0x7F is NaN
+    static constexpr float qmax = 448.0f;
 };
+template <>
+struct MxFmt<DFQ_MX_FP6_E2M3> {   // s ee mmm, bias 1: every code is finite
+    static constexpr int mbits = 3, emin = 0, emax = 2, max_code = 0x1F, sign = 0x20;
+    static constexpr float qmax = 7.5f;
+};
+template <>
+struct MxFmt<DFQ_MX_FP6_E3M2> {   // s eee mm, bias 3: every code is finite
+    static constexpr int mbits = 2, emin = -2, emax = 4, max_code = 0x1F, sign = 0x20;
+    static constexpr float qmax = 28.0f;
+};
+template <int FMT>
+constexpr bool kMxFp6 = FMT == DFQ_MX_FP6_E2M3 || FMT == DFQ_MX_FP6_E3M2;
 
 __device__ __forceinline__ float pow2f(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }   // -127 <= e <= 127; -127: +0
 
@@ -72,7 +88,7 @@ __device__ __forceinline__ uint32_t mx_encode(float x, float inv, float up, floa
     float q = n * pow2f(e - F::mbits);
     if (code > (uint32_t)F::max_code) {
         code = F::max_code;
-        q = FMT == DFQ_MX_FP4_E2M1 ? 6.0f : 448.0f;
+        q = F::qmax;
     }
     const uint32_t sb = xb & 0x80000000u;
     y = __uint_as_float(__float_as_uint(q * up) | sb);
@@ -86,6 +102,11 @@ __device__ __forceinline__ uint32_t max8(uint32_t m) {
     x = max(x, __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false));
     x = max(x, __builtin_amdgcn_update_dpp(x, x, 0x141, 0xF, 0xF, false));
     return (uint32_t)x;
+}
+
+// the value of the lane's right-hand neighbour in its quad (lane 3: of lane 0)
+__device__ __forceinline__ uint32_t quad_next(uint32_t w) {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)w, (int)w, 0x39, 0xF, 0xF, false);
 }
 
 // The wave's task.  vtotal padded elements; padded element v lies in row
@@ -113,7 +134,8 @@ __device__ __forceinline__ void mx_task(const MxJob& J, const MxTask& t, float* 
     const DFQ_GLOBAL float* src = (const DFQ_GLOBAL float*)J.src + ebase;
     DFQ_GLOBAL float* dst = (DFQ_GLOBAL float*)J.dst + ebase;
     DFQ_GLOBAL float* esum = (DFQ_GLOBAL float*)J.esum + ebase;   // khw == 1 (the LDS sums index from J.esum)
-    DFQ_GLOBAL uint8_t* codes = (DFQ_GLOBAL uint8_t*)J.codes + (FMT == DFQ_MX_FP4_E2M1 ? vbase >> 1 : vbase);
+    DFQ_GLOBAL uint8_t* codes = (DFQ_GLOBAL uint8_t*)J.codes +
+                                (FMT == DFQ_MX_FP4_E2M1 ? vbase >> 1 : kMxFp6<FMT> ? (vbase >> 2) * 3 : vbase);   // vbase % 32 == 0
     DFQ_GLOBAL uint8_t* scales = (DFQ_GLOBAL uint8_t*)J.scales + (vbase >> 5);
     const bool want_d = J.dst != nullptr, want_c = J.codes != nullptr, want_s = J.scales != nullptr;
     const bool want_e = J.esum != nullptr, lds_e = J.lds_esum != 0;
@@ -156,6 +178,18 @@ __device__ __forceinline__ void mx_task(const MxJob& J, const MxTask& t, float* 
             uint32_t c[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) c[j] = mx_encode<FMT>(x[b][j], inv, up, y[j]);
+            // FP6: a lane's codes are the 24 bits w, a quad's 16 elements three dwords
+            //   d0 = w0 | w1 << 24,  d1 = w1 >> 8 | w2 << 16,  d2 = w2 >> 16 | w3 << 8
+            // lanes 0..2 of the quad build one each from their own w and their neighbour's (every
+            // lane takes part; vtotal % 32 == 0, so a quad lies inside the task or outside it)
+            uint32_t w6 = 0, d6 = 0;
+            if (kMxFp6<FMT>) {
+                w6 = c[0] | (c[1] << 6) | (c[2] << 12) | (c[3] << 18);
+                if (VEC) {
+                    const int sh = 8 * (lane & 3);
+                    d6 = (w6 >> sh) | (quad_next(w6) << (24 - sh));   // lane 3: not stored
+                }
+            }
             if (v >= vtotal) continue;
             // v numbers the task's padded elements: it addresses the codes and scales
             if (want_c) {
@@ -166,6 +200,15 @@ __device__ __forceinline__ void mx_task(const MxJob& J, const MxTask& t, float* 
                     } else {
                         codes[v >> 1] = (uint8_t)lo;
                         codes[(v >> 1) + 1] = (uint8_t)hi;
+                    }
+                } else if (kMxFp6<FMT>) {
+                    if (VEC) {   // 48 consecutive dwords per wave round
+                        if ((lane & 3) != 3) *(DFQ_GLOBAL uint32_t*)(codes + (v >> 4) * 12 + 4 * (lane & 3)) = d6;
+                    } else {
+                        DFQ_GLOBAL uint8_t* p = codes + (v >> 2) * 3;
+                        p[0] = (uint8_t)w6;
+                        p[1] = (uint8_t)(w6 >> 8);
+                        p[2] = (uint8_t)(w6 >> 16);
                     }
                 } else {
                     if (VEC) {
@@ -233,6 +276,12 @@ __device__ __forceinline__ void mx_task(const MxJob& J, const MxTask& t, float* 
 
 // LDS (dynamic): DFQ_MX_ESUM_TASK_ELEMS floats per wave when some tensor's error sums
 // need them, none otherwise; written and read by its own wave only.
+// FP4 and FP8 tasks run in mx_quantize_kernel, FP6 tasks in mx6_quantize_kernel: four
+// mx_task instantiations each (all eight in one kernel take 167 VGPRs and spill SGPRs;
+// apart, 133 as before the FP6 formats and 149, no scratch, 3 waves per SIMD).  The
+// host hands each kernel its own tasks (dfq_mx_quantize_batch).  The two bodies are
+// written out: through one shared template the compiler schedules mx_quantize_kernel
+// differently, and it is kept instruction for instruction what it was without FP6.
 __global__ __launch_bounds__(kThreads) void mx_quantize_kernel(const MxJob* __restrict__ jobs,
                                                                const MxTask* __restrict__ tasks, int64_t n_tasks) {
     extern __shared__ __attribute__((aligned(16))) float mx_lds[];
@@ -253,11 +302,32 @@ __global__ __launch_bounds__(kThreads) void mx_quantize_kernel(const MxJob* __re
     }
 }
 
+__global__ __launch_bounds__(kThreads) void mx6_quantize_kernel(const MxJob* __restrict__ jobs,
+                                                                const MxTask* __restrict__ tasks, int64_t n_tasks) {
+    extern __shared__ __attribute__((aligned(16))) float mx_lds[];
+    float* const edata = mx_lds + (threadIdx.x >> 6) * DFQ_MX_ESUM_TASK_ELEMS;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t wave = (int64_t)blockIdx.x * kMxWaves + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kMxWaves;
+    for (int64_t ti = wave; ti < n_tasks; ti += n_waves) {
+        const MxTask t = tasks[ti];
+        const MxJob J = jobs[t.job];
+        if (J.format == DFQ_MX_FP6_E2M3) {
+            if (J.vec) mx_task<DFQ_MX_FP6_E2M3, true>(J, t, edata, lane);
+            else mx_task<DFQ_MX_FP6_E2M3, false>(J, t, edata, lane);
+        } else {
+            if (J.vec) mx_task<DFQ_MX_FP6_E3M2, true>(J, t, edata, lane);
+            else mx_task<DFQ_MX_FP6_E3M2, false>(J, t, edata, lane);
+        }
+    }
+}
+
 }  // namespace
 
 hipError_t preload_mx() {   // see dfq_preload
     hipFuncAttributes a;
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(mx_quantize_kernel));
+    const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(mx_quantize_kernel));
+    return e != hipSuccess ? e : hipFuncGetAttributes(&a, reinterpret_cast<const void*>(mx6_quantize_kernel));
 }
 
 }  // namespace dfq
@@ -276,19 +346,36 @@ extern "C" int dfq_mx_quantize_batch(const dfq_mx_desc* d, int32_t n, void* ws, 
     char* base = static_cast<char*>(ws);
     std::vector<char> blob((size_t)L.total, 0);   // one staging blob (jobs, tasks), one copy
     MxJob* hj = reinterpret_cast<MxJob*>(blob.data() + L.o_jobs);
-    for (int32_t p = 0; p < n; ++p)
+    const auto fp6 = [&](int32_t p) { return d[p].format == DFQ_MX_FP6_E2M3 || d[p].format == DFQ_MX_FP6_E3M2; };
+    bool lds_of[2] = {false, false};   // [the FP4 / FP8 tasks, the FP6 tasks]: some error sums go through LDS
+    int32_t n_fp6 = 0;
+    for (int32_t p = 0; p < n; ++p) {
+        lds_of[fp6(p)] |= mx_lds_esum(d[p]);
+        n_fp6 += fp6(p);
         hj[p] = MxJob{d[p].src, d[p].dst, d[p].codes, d[p].scales, d[p].esum, d[p].row_len, mx_blocks(d[p].row_len),
                       mx_split(d[p]) ? mx_piece_len(d[p]) : 0, d[p].khw, d[p].format, mx_vec(d[p]) ? 1 : 0,
                       mx_lds_esum(d[p]) ? 1 : 0};
+    }
+    // one launch per kernel that has tasks.  A list of one kind (the usual call) keeps its table
+    // as planned; a mixed one keeps the list order inside each kind, the FP6 tasks behind the others
+    int64_t n_first = n_fp6 == 0 ? L.n_tasks : 0;
+    if (n_fp6 != 0 && n_fp6 != n)
+        n_first = std::stable_partition(tasks.begin(), tasks.end(), [&](const MxTask& t) { return !fp6(t.job); }) -
+                  tasks.begin();
     std::memcpy(blob.data() + L.o_tasks, tasks.data(), sizeof(MxTask) * tasks.size());
     hipStream_t s = static_cast<hipStream_t>(stream);
     DFQ_HIP_CHECK(stage_h2d(base, blob.data(), blob.size(), s));
-    // one wave per task up to 2^18 tasks: blocks dispatched as others retire balance the uneven tasks
-    const int grid = (int)std::min<int64_t>(ceil_div(L.n_tasks, (int64_t)kMxWaves), 1 << 16);
-    const size_t lds = L.lds_jobs > 0 ? sizeof(float) * kMxWaves * DFQ_MX_ESUM_TASK_ELEMS : 0;
-    hipLaunchKernelGGL(mx_quantize_kernel, dim3(grid), dim3(kThreads), lds, s,
-                       reinterpret_cast<const MxJob*>(base + L.o_jobs),
-                       reinterpret_cast<const MxTask*>(base + L.o_tasks), L.n_tasks);
-    DFQ_LAUNCH_CHECK();
+    const MxJob* dj = reinterpret_cast<const MxJob*>(base + L.o_jobs);
+    const MxTask* dt = reinterpret_cast<const MxTask*>(base + L.o_tasks);
+    for (int k = 0; k < 2; ++k) {
+        const int64_t first = k == 0 ? 0 : n_first, count = k == 0 ? n_first : L.n_tasks - n_first;
+        if (count == 0) continue;
+        // one wave per task up to 2^18 tasks: blocks dispatched as others retire balance the uneven tasks
+        const int grid = (int)std::min<int64_t>(ceil_div(count, (int64_t)kMxWaves), 1 << 16);
+        const size_t lds = lds_of[k] ? sizeof(float) * kMxWaves * DFQ_MX_ESUM_TASK_ELEMS : 0;
+        hipLaunchKernelGGL(k == 0 ? mx_quantize_kernel : mx6_quantize_kernel, dim3(grid), dim3(kThreads), lds, s, dj,
+                           dt + first, count);
+        DFQ_LAUNCH_CHECK();
+    }
     return DFQ_OK;
 }

@@ -11,7 +11,9 @@ static int mx_check(const dfq_mx_desc& p) {
     if (!p.src || addr(p.src) % 4 || addr(p.dst) % 4 || addr(p.esum) % 4) return DFQ_ERR_INVALID;
     if (!p.dst && !p.codes && !p.scales && !p.esum) return DFQ_ERR_INVALID;
     if (p.rows < 1 || p.row_len < 1 || p.khw < 1) return DFQ_ERR_INVALID;
-    if (p.format != DFQ_MX_FP4_E2M1 && p.format != DFQ_MX_FP8_E4M3) return DFQ_ERR_INVALID;
+    if (p.format != DFQ_MX_FP4_E2M1 && p.format != DFQ_MX_FP8_E4M3 && p.format != DFQ_MX_FP6_E2M3 &&
+        p.format != DFQ_MX_FP6_E3M2)
+        return DFQ_ERR_INVALID;
     if (p.flags != 0) return DFQ_ERR_INVALID;
     // element, code and task indices stay far inside int64
     if (p.rows > (int64_t(1) << 40) || p.row_len > (int64_t(1) << 40) || p.rows > (int64_t(1) << 50) / p.row_len)

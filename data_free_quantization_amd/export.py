@@ -11,9 +11,10 @@ metadata (bits, granularity, symmetric, clip, shapes).  ``load(path)`` returns
 the tensors; ``dequantize(entry)`` rebuilds the fp32 weight exactly as the sweep
 did: ``clamp(fl(fl(q * s) + zero), clip)``.
 
-With ``weight_format="mxfp4"`` / ``"mxfp8"`` (an MX state of ``quantize_targ_layer``)
-the file holds ``k.codes`` (uint8 [rows, nb, 16] packed FP4 nibbles or [rows, nb, 32]
-FP8 bytes), ``k.scales`` (uint8 E8M0 [rows, nb], one per 32 elements of a row) and
+With ``weight_format="mxfp4"`` / ``"mxfp6_e2m3"`` / ``"mxfp6_e3m2"`` / ``"mxfp8"`` (an MX
+state of ``quantize_targ_layer``) the file holds ``k.codes`` (uint8 [rows, nb, 16]
+packed FP4 nibbles, [rows, nb, 24] densely packed FP6 codes or [rows, nb, 32] FP8
+bytes; ``code_storage`` names which), ``k.scales`` (uint8 E8M0 [rows, nb], one per 32 elements of a row) and
 ``k.bias``; the metadata adds ``weight_format`` and ``mx_block``, and ``dequantize``
 dispatches on it (``mx.mx_dequantize``: ``+-q * 2^(scale - 127)``, exact).
 """
@@ -52,6 +53,10 @@ def save(path, graph, state: Dict, *, bits: int, granularity: str, symmetric: bo
     return layers
 
 
+_MX_STORAGE = {"mxfp4": "fp4_nibbles", "mxfp8": "fp8_e4m3", "mxfp6_e2m3": "fp6_e2m3_packed",
+               "mxfp6_e3m2": "fp6_e3m2_packed"}
+
+
 def _save_mx(path, graph, state, weight_format, clip):
     from . import mx
     tensors, layers = {}, {}
@@ -67,7 +72,7 @@ def _save_mx(path, graph, state, weight_format, clip):
         layers[k] = {"shape": list(layer.weight.shape), "type": type(layer).__name__}
     meta = {"format": "dfq-mi355x/1", "weight_format": weight_format, "mx_block": mx.BLOCK,
             "bits_per_weight": mx.bits_per_weight(weight_format), "clip": list(clip) if clip is not None else None,
-            "code_storage": "fp4_nibbles" if weight_format == "mxfp4" else "fp8_e4m3", "layers": layers}
+            "code_storage": _MX_STORAGE[weight_format], "layers": layers}
     save_file({n: t.cpu() for n, t in tensors.items()}, str(path), metadata={"dfq": json.dumps(meta)})
     return layers
 

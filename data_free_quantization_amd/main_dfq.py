@@ -25,11 +25,12 @@ Same flags and stage order; the transforms run on the GPU.  Additive flags:
                        The defaults (16, 0.5) are interface choices: no dataset ships
                        here to tune them on.  --report then counts, per layer, the units
                        that chose a narrower range and those at the narrowest candidate
-  --weight_format {int,mxfp4,mxfp8}   int (default): the integer grid of --bits_weight /
-                       --granularity / --symmetric.  mxfp4 / mxfp8: OCP MX block-scaled
-                       weights (mx.py: FP4 E2M1 / FP8 E4M3 elements, one power-of-two scale
-                       per 32 elements of a row; 4.25 / 8.25 bits per weight), to which those
-                       three flags do not apply.  Not with --clip_search, --bc_mode reference,
+  --weight_format {int,mxfp4,mxfp6_e2m3,mxfp6_e3m2,mxfp8}   int (default): the integer grid
+                       of --bits_weight / --granularity / --symmetric.  mxfp4 / mxfp6_e2m3 /
+                       mxfp6_e3m2 / mxfp8: OCP MX block-scaled weights (mx.py: FP4 E2M1 / FP6
+                       E2M3 / FP6 E3M2 / FP8 E4M3 elements, one power-of-two scale per 32
+                       elements of a row; 4.25 / 6.25 / 6.25 / 8.25 bits per weight), to which
+                       those three flags do not apply.  There is no bare mxfp6.  Not with --clip_search, --bc_mode reference,
                        --clip_weight under --bc_mode fused, or --world_size > 1
 
 Example (README.md:137 of the reference):
@@ -98,8 +99,8 @@ def get_argument(argv=None):
     p.add_argument("--clip_candidates", type=int, default=16, help="candidate ranges per unit (1..64)")
     p.add_argument("--clip_min_frac", type=float, default=0.5,
                    help="the narrowest candidate as a share of the min-max range, in [0, 1]")
-    p.add_argument("--weight_format", default="int", choices=["int", "mxfp4", "mxfp8"],
-                   help="weight codes: the integer grid, or OCP MX block-scaled FP4 / FP8 (32-element blocks)")
+    p.add_argument("--weight_format", default="int", choices=["int", "mxfp4", "mxfp6_e2m3", "mxfp6_e3m2", "mxfp8"],
+                   help="weight codes: the integer grid, or OCP MX block-scaled FP4 / FP6 / FP8 (32-element blocks)")
     args = p.parse_args(argv)
     if args.weight_format != "int":
         if not args.quantize:

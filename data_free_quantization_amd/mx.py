@@ -1,9 +1,9 @@
-"""OCP Microscaling (MX) block-scaled weight quantization: MXFP4 and MXFP8.
+"""OCP Microscaling (MX) block-scaled weight quantization: MXFP4, MXFP6 and MXFP8.
 
 Host wrapper of ``dfq_mx_quantize_batch`` (include/dfq_hip.h): FP4
-(E2M1) or FP8 (E4M3) elements with one shared power-of-two E8M0 scale per 32
-consecutive elements of a row, the operand format of CDNA4's scaled matrix
-instructions.  ``mx_quantize`` takes every tensor of a list in one C call (one
+(E2M1), FP6 (E2M3 or E3M2) or FP8 (E4M3) elements with one shared power-of-two E8M0
+scale per 32 consecutive elements of a row, the operand format of CDNA4's scaled
+matrix instructions.  ``mx_quantize`` takes every tensor of a list in one C call (one
 launch, one HBM pass, asynchronous on the stream); ``mx_dequantize`` rebuilds the
 fp32 values from codes and scales in plain torch, exactly, on CPU or GPU.  There is
 no CPU fallback for the quantizer: CPU tensors raise."""
@@ -20,7 +20,9 @@ from . import _lib
 
 BLOCK = _lib.DFQ_MX_BLOCK
 #: weight_format name -> (library format, element bits, code bytes per block)
-FORMATS = {"mxfp4": (_lib.DFQ_MX_FP4_E2M1, 4, 16), "mxfp8": (_lib.DFQ_MX_FP8_E4M3, 8, 32)}
+FORMATS = {"mxfp4": (_lib.DFQ_MX_FP4_E2M1, 4, 16), "mxfp8": (_lib.DFQ_MX_FP8_E4M3, 8, 32),
+           "mxfp6_e2m3": (_lib.DFQ_MX_FP6_E2M3, 6, 24), "mxfp6_e3m2": (_lib.DFQ_MX_FP6_E3M2, 6, 24)}
+_NAMES = "'mxfp4', 'mxfp6_e2m3', 'mxfp6_e3m2' or 'mxfp8'"   # there is no bare 'mxfp6': the two differ
 
 
 def is_mx(weight_format: str) -> bool:
@@ -28,12 +30,12 @@ def is_mx(weight_format: str) -> bool:
     if weight_format == "int":
         return False
     if weight_format not in FORMATS:
-        raise ValueError("weight_format must be 'int', 'mxfp4' or 'mxfp8', got %r" % (weight_format,))
+        raise ValueError("weight_format must be 'int', %s, got %r" % (_NAMES, weight_format))
     return True
 
 
 def bits_per_weight(fmt: str) -> float:
-    """Element bits plus the block's share of its 8-bit scale: 4.25 or 8.25."""
+    """Element bits plus the block's share of its 8-bit scale: 4.25, 6.25 or 8.25."""
     return FORMATS[fmt][1] + 8.0 / BLOCK
 
 
@@ -49,7 +51,8 @@ class MXItem:
     """One fp32 tensor viewed as [rows, -1] (rows = shape[0] unless given) and what
     to write for it.  The outputs may also be raw device addresses (int) into
     memory the caller keeps alive until the call has run.  ``codes``: uint8
-    [rows, nb, 16] (mxfp4, element 2k in the low nibble) or [rows, nb, 32] (mxfp8);
+    [rows, nb, 16] (mxfp4, element 2k in the low nibble), [rows, nb, 32] (mxfp8) or
+    [rows, nb, 24] (mxfp6_*: 32 six-bit codes packed densely, element i in bits [6i, 6i+6));
     ``scales``: uint8 [rows, nb]; ``esum``: fp32 [numel / khw]; nb = ceil(row_len / 32)."""
     src: torch.Tensor
     fmt: str = "mxfp4"
@@ -94,7 +97,7 @@ def mx_quantize(items: Sequence[MXItem], stream: Optional[torch.cuda.Stream] = N
         if it.src.device != items[0].src.device:
             raise ValueError("every tensor of an mx_quantize call must live on one device")
         if it.fmt not in FORMATS:
-            raise ValueError("fmt must be 'mxfp4' or 'mxfp8', got %r" % (it.fmt,))
+            raise ValueError("fmt must be %s, got %r" % (_NAMES, it.fmt))
         if it.src.numel() == 0:
             raise ValueError("empty tensors have nothing to quantize")
         for name in ("codes", "scales"):
@@ -138,6 +141,14 @@ def _tables(fmt: str, device) -> torch.Tensor:
     """Value of every code (sign included), fp32."""
     if fmt == "mxfp4":
         mag = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0], dtype=torch.float32)
+    elif fmt == "mxfp6_e2m3":   # s ee mmm, bias 1: m / 8, (8 + m) * 2^(e - 4)
+        c = torch.arange(32, dtype=torch.int32)
+        e, m = c >> 3, (c & 7).to(torch.float32)
+        mag = torch.where(e == 0, m * 2.0 ** -3, (8.0 + m) * torch.pow(2.0, (e - 4).to(torch.float32)))
+    elif fmt == "mxfp6_e3m2":   # s eee mm, bias 3: m / 16, (4 + m) * 2^(e - 5)
+        c = torch.arange(32, dtype=torch.int32)
+        e, m = c >> 2, (c & 3).to(torch.float32)
+        mag = torch.where(e == 0, m * 2.0 ** -4, (4.0 + m) * torch.pow(2.0, (e - 5).to(torch.float32)))
     else:
         c = torch.arange(128, dtype=torch.int32)
         e, m = c >> 3, (c & 7).to(torch.float32)
@@ -146,12 +157,27 @@ def _tables(fmt: str, device) -> torch.Tensor:
     return torch.cat([mag, -mag]).to(device)
 
 
+def pack6(c: torch.Tensor) -> torch.Tensor:
+    """[..., 4k] six-bit codes -> [..., 3k] bytes: four codes w = c0 | c1 << 6 | c2 << 12 |
+    c3 << 18 are the bytes w & 0xFF, (w >> 8) & 0xFF, w >> 16 (the FP6 ``codes`` layout)."""
+    q = c.to(torch.int64).reshape(*c.shape[:-1], -1, 4)
+    w = q[..., 0] | (q[..., 1] << 6) | (q[..., 2] << 12) | (q[..., 3] << 18)
+    return torch.stack([w & 0xFF, (w >> 8) & 0xFF, w >> 16], dim=-1).reshape(*c.shape[:-1], -1).to(torch.uint8)
+
+
+def unpack6(b: torch.Tensor) -> torch.Tensor:
+    """The inverse of ``pack6``: [..., 3k] bytes -> [..., 4k] six-bit codes (int64)."""
+    t = b.to(torch.int64).reshape(*b.shape[:-1], -1, 3)
+    w = t[..., 0] | (t[..., 1] << 8) | (t[..., 2] << 16)
+    return torch.stack([w & 0x3F, (w >> 6) & 0x3F, (w >> 12) & 0x3F, w >> 18], dim=-1).reshape(*b.shape[:-1], -1)
+
+
 def mx_dequantize(codes: torch.Tensor, scales: torch.Tensor, shape, fmt: str) -> torch.Tensor:
-    """The fp32 tensor of ``shape`` that ``codes`` ([rows, nb, 16 | 32] uint8) and
+    """The fp32 tensor of ``shape`` that ``codes`` ([rows, nb, 16 | 24 | 32] uint8) and
     ``scales`` ([rows, nb] uint8) stand for: y = +-q * 2^(scale - 127), every step
     exact in fp32 -- bit for bit the ``dst`` of ``mx_quantize``.  Pure torch, CPU or GPU."""
     if fmt not in FORMATS:
-        raise ValueError("fmt must be 'mxfp4' or 'mxfp8', got %r" % (fmt,))
+        raise ValueError("fmt must be %s, got %r" % (_NAMES, fmt))
     n = 1
     for s in shape:
         n *= int(s)
@@ -159,6 +185,8 @@ def mx_dequantize(codes: torch.Tensor, scales: torch.Tensor, shape, fmt: str) ->
     c = codes.reshape(rows, nb, FORMATS[fmt][2]).to(torch.int64)
     if fmt == "mxfp4":
         c = torch.stack([c & 0xF, c >> 4], dim=-1)   # element 2k low, 2k + 1 high
+    elif FORMATS[fmt][1] == 6:
+        c = unpack6(c)
     q = _tables(fmt, codes.device)[c.reshape(rows, nb, BLOCK)]
     # 2^(scale - 127) from its bit pattern (byte 0, only written for an all-zero block, reads as 0)
     up = (scales.to(torch.int32) << 23).view(torch.float32)

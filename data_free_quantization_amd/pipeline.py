@@ -47,8 +47,9 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
     against the unclamped weights); needs ``quantize``.  Bias correction sees the
     clamped weight as its input.
     ``weight_format``: "int" (the integer grid of ``bits_weight`` / ``granularity`` /
-    ``symmetric``), or "mxfp4" / "mxfp8": OCP MX block-scaled weights (mx.py), to which
-    those three do not apply.  An MX format raises ValueError with ``clip_search`` (the
+    ``symmetric``), or "mxfp4" / "mxfp6_e2m3" / "mxfp6_e3m2" / "mxfp8": OCP MX block-scaled
+    weights (mx.py; 4.25 / 6.25 / 6.25 / 8.25 bits per weight), to which those three do
+    not apply.  An MX format raises ValueError with ``clip_search`` (the
     search measures integer grids), with ``bc_mode="reference"`` (its error term is the
     integer quantizer's) and with ``clip`` under ``bc_mode="fused"`` (the MX pass has no
     fused clamp); ``clip`` as its own stage after quantization stays, in the reference's

@@ -227,8 +227,9 @@ def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, *, gr
     rank every result, and each rank writes them back into its parameters
     (distributed.ShardedSweep).  Results are identical to the unsharded call.
 
-    ``weight_format="mxfp4"`` / ``"mxfp8"``: the weights take OCP MX block-scaled
-    codes instead of an integer grid (mx.mx_quantize: FP4 / FP8 elements, one
+    ``weight_format="mxfp4"`` / ``"mxfp6_e2m3"`` / ``"mxfp6_e3m2"`` / ``"mxfp8"``: the
+    weights take OCP MX block-scaled codes instead of an integer grid (mx.mx_quantize:
+    FP4 / FP6 / FP8 elements -- ``codes`` [O, nb, 16 | 24 | 24 | 32] bytes --, one
     power-of-two scale per 32 elements of a row; all layers in one launch);
     ``bit_weight``, ``granularity`` and ``symmetric`` then do not apply to them, and
     ``clip``, ``shard=True`` and ``weight_ranges`` raise ValueError.  Biases take the

@@ -426,19 +426,27 @@ int dfq_clip_search_batch(const dfq_clip_search_desc* descs, int32_t n, void* ws
  * Every row of the [rows, row_len] view is cut into blocks of DFQ_MX_BLOCK = 32
  * consecutive elements, nb = ceil(row_len / 32) per row (blocks never cross rows; a
  * last partial block behaves as if padded with +0).  Element formats: FP4 E2M1
- * (magnitudes 0 0.5 1 1.5 2 3 4 6, emax 2) and FP8 E4M3 "fn" (bias 7, subnormals,
- * maximum 448, no infinities, emax 8).  For one block of fp32 elements x_i:
+ * (magnitudes 0 0.5 1 1.5 2 3 4 6, emax 2), FP8 E4M3 "fn" (bias 7, subnormals,
+ * maximum 448, no infinities, emax 8), FP6 E2M3 (bias 1, subnormals m/8, normals
+ * (8+m) * 2^(e-4), maximum 7.5, emax 2) and FP6 E3M2 (bias 3, subnormals m/16, normals
+ * (4+m) * 2^(e-5), maximum 28, emax 4); the FP6 formats have no infinity or NaN code.
+ * For one block of fp32 elements x_i:
  *   amax = max |x_i|;  X = amax == 0 ? -127 : clamp(floor(log2 amax) - emax, -127, 127)
  *   scale byte = X + 127 (E8M0; 0xFF is never written)
  *   q_i  = |x_i| * 2^-X rounded to the nearest magnitude of the format, ties to the
- *          even code, saturating at the maximum (6 or 448; no E4M3 NaN code)
+ *          even code, saturating at the maximum (6, 448, 7.5 or 28; no E4M3 NaN code)
  *   code = the sign bit of x_i (kept by -0 and by values that round to zero) above
- *          q_i's encoding: a nibble `s e e m`, or a byte `s eeee mmm`
+ *          q_i's encoding: a nibble `s e e m`, a byte `s eeee mmm`, or six bits
+ *          `s ee mmm` (E2M3) / `s eee mm` (E3M2)
  *   y_i  = +-q_i * 2^X (exact in fp32)
  * Outputs, each optional (not all NULL):
  *   dst    fp32 y, [rows, row_len]; may alias src
  *   codes  uint8 [rows, nb, 16] (FP4: element 2k in the low nibble, 2k+1 in the high
- *          one) or [rows, nb, 32] (FP8); the padding of a partial block is +0 codes
+ *          one), [rows, nb, 32] (FP8) or [rows, nb, 24] (FP6: the block's 32 codes packed
+ *          densely, little-endian -- element i is bits [6i, 6i+6) of the block's 192-bit
+ *          string, byte b its bits [8b, 8b+8); four elements w = c0 | c1<<6 | c2<<12 |
+ *          c3<<18 are the bytes w & 0xFF, (w>>8) & 0xFF, w>>16); the padding of a partial
+ *          block is +0 codes
  *   scales uint8 [rows, nb]
  *   esum   fp32 [rows * row_len / khw], the sweep's E[p] = sum_{k<khw} fl32(y - x)[p*khw + k]
  *          in ATen's CPU order; row_len % khw != 0 with esum set: DFQ_ERR_SHAPE
@@ -448,6 +456,7 @@ int dfq_clip_search_batch(const dfq_clip_search_desc* descs, int32_t n, void* ws
  * is added by one lane in a fixed order, and no atomic is used. */
 enum { DFQ_MX_BLOCK = 32 };
 enum { DFQ_MX_FP4_E2M1 = 0, DFQ_MX_FP8_E4M3 = 1 };
+enum { DFQ_MX_FP6_E2M3 = 0x23, DFQ_MX_FP6_E3M2 = 0x32 };   /* (exponent bits, mantissa bits); 2 is no format */
 /* Elements one wave task holds at most; with esum and khw > 1 (the errors wait in
  * LDS for their sums) DFQ_MX_ESUM_TASK_ELEMS.  A row longer than that is cut into
  * pieces that are multiples of 32 and, with such an esum, of khw: when no such
@@ -463,13 +472,14 @@ typedef struct dfq_mx_desc {
     int64_t      rows;     /* >= 1 */
     int64_t      row_len;  /* >= 1 */
     int32_t      khw;      /* >= 1; spatial size for esum (1 for Linear / 1x1) */
-    int32_t      format;   /* DFQ_MX_FP4_E2M1 | DFQ_MX_FP8_E4M3 */
+    int32_t      format;   /* DFQ_MX_FP4_E2M1 | DFQ_MX_FP8_E4M3 | DFQ_MX_FP6_E2M3 | DFQ_MX_FP6_E3M2 */
     int32_t      flags;    /* 0 */
     int32_t      reserved;
 } dfq_mx_desc;
 /* Device workspace bytes for dfq_mx_quantize_batch (-1: bad arguments). */
 int64_t dfq_mx_quantize_ws_bytes(const dfq_mx_desc* descs, int32_t n);
-/* Every tensor of the list in one launch and one HBM pass, asynchronous on `stream`,
+/* Every tensor of the list in one launch (two for a list that mixes FP6 tensors with
+ * FP4 / FP8 ones) and one HBM pass, asynchronous on `stream`,
  * no host wait (the tables go up through the library's pinned staging ring).  ws as
  * for dfq_clip_search_batch: >= dfq_mx_quantize_ws_bytes bytes, 256-B aligned,
  * stream-ordered with `stream`; DFQ_ERR_WORKSPACE if it is NULL or too small,

@@ -8,15 +8,18 @@ bench's sweep (per-channel INT8 with its codes and error sums) on the same list,
 the same process, alternated three times with the MX calls; every timed call sits
 inside a HIP event pair (the table upload and the launch), median of --steps calls
 after --warmup.  Fractions are algorithmic bytes (computed here from the shapes:
-read 4, write 4 + 0.5 | 1 of codes + 1/32 of scales per padded element + 4/khw of
+read 4, write 4 + 0.5 | 0.75 | 1 of codes + 1/32 of scales per padded element + 4/khw of
 error sums) over time over the 8 TB/s HBM peak; the sweep's are its plan's
 algo_bytes.  A whole call over peak is an end-to-end figure (it holds the table
 upload), not the kernel's share.  One weight set alone is timed the same way, in
 microseconds.  The JSON line goes to stdout and to --out.
 
-  python scripts/mx_quantize_time.py             # -> profiles/r09/mx_quantize_time.jsonl
+  python scripts/mx_quantize_time.py             # -> profiles/r10/mx6_quantize_time.jsonl
   python scripts/mx_quantize_time.py --quality   # MobileNetV2 model SQNR per format, with and
-                                                 #   without equalization -> profiles/r09/quality_mx.jsonl
+                                                 #   without equalization -> profiles/r10/quality_mx6.jsonl
+  python scripts/mx_quantize_time.py --ab OTHER.so   # MXFP4 / MXFP8 call times of another build of the
+                                                 #   library (the parent commit's) against this tree's, alternated
+                                                 #   three times in this process -> profiles/r10/mx6_parent_ab.jsonl
 """
 import argparse
 import ctypes as C
@@ -32,7 +35,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import bench  # noqa: E402
 from data_free_quantization_amd import _lib, distributed as D, mx  # noqa: E402
 
-OUT = Path(__file__).resolve().parent.parent / "profiles" / "r09"
+OUT = Path(__file__).resolve().parent.parent / "profiles" / "r10"
 
 
 def emit(records, path):
@@ -50,17 +53,24 @@ def timed(run, stream, warmup, steps):
 
 class MxCall:
     """A prepared dfq_mx_quantize_batch call over sweep items: the descriptor table,
-    the code and scale arenas and the workspace; run() is the one C call."""
+    the code and scale arenas and the workspace; run() is the one C call.  ``share``:
+    an MXFP8 call over the same items whose arenas and workspace this one writes too --
+    where a buffer lies moves a call's time by percents, more than the formats differ."""
 
-    def __init__(self, items, fmt):
+    def __init__(self, items, fmt, share=None):
+        self._lib = _lib.load()
         dev = items[0].src.device
         cb = mx.FORMATS[fmt][2]
         geo = []
         for it in items:
             rows = it.src.shape[0]
             geo.append((rows, it.src.numel() // rows, mx.blocks(it.src.numel() // rows)))
-        self.codes = torch.empty(sum(r * nb * cb for r, _, nb in geo), dtype=torch.uint8, device=dev)
-        self.scales = torch.empty(sum(-(-r * nb // 16) * 16 for r, _, nb in geo), dtype=torch.uint8, device=dev)
+        if share is not None:
+            self.codes, self.scales = share.codes, share.scales
+        else:
+            self.codes = torch.empty(sum(r * nb * cb for r, _, nb in geo), dtype=torch.uint8, device=dev)
+            self.scales = torch.empty(sum(-(-r * nb // 16) * 16 for r, _, nb in geo), dtype=torch.uint8, device=dev)
+        assert self.codes.numel() >= sum(r * nb * cb for r, _, nb in geo)
         tab, co, so, self.algo_bytes = [], 0, 0, 0
         for it, (rows, row_len, nb) in zip(items, geo):
             tab.append((it.src.data_ptr(), it.dst.data_ptr(), self.codes.data_ptr() + co, self.scales.data_ptr() + so,
@@ -72,17 +82,20 @@ class MxCall:
         self._tab = np.array(tab, dtype=mx._MX)
         self._descs = self._tab.ctypes.data_as(C.POINTER(_lib.MxDesc))
         self._n = len(items)
-        nb_ws = int(_lib.load().dfq_mx_quantize_ws_bytes(self._descs, self._n))
+        nb_ws = int(self._lib.dfq_mx_quantize_ws_bytes(self._descs, self._n))
         assert nb_ws > 0
-        self._ws = torch.empty(nb_ws, dtype=torch.uint8, device=dev)
+        self._ws = share._ws if share is not None else torch.empty(nb_ws, dtype=torch.uint8, device=dev)
+        assert self._ws.numel() >= nb_ws
         self.ws_bytes = nb_ws
 
-    def run(self, stream):
-        _lib.check(_lib.load().dfq_mx_quantize_batch(self._descs, self._n, self._ws.data_ptr(), self._ws.numel(),
+    def run(self, stream, lib=None):
+        """The call, through this process's library or another build of it (same buffers)."""
+        _lib.check((lib or self._lib).dfq_mx_quantize_batch(self._descs, self._n, self._ws.data_ptr(), self._ws.numel(),
                                                      C.c_void_p(stream.cuda_stream)), "dfq_mx_quantize_batch")
 
 
-def timing(args):
+def bench_list(args):
+    """The bench headline's sweep items on the GPU and what describes them."""
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     _lib.preload()
@@ -94,10 +107,17 @@ def timing(args):
     specs = D.uniform_specs(shapes * copies, bits=b.bits, per_channel=per_channel, symmetric=symmetric,
                             want_esum=not b.no_esum, clip=(-15.0, 15.0))
     items = bench.make_list(specs, range(len(specs)), dev, 1234)
+    return dev, b, shapes, per_copy, copies, symmetric, items
+
+
+def timing(args):
+    dev, b, shapes, per_copy, copies, symmetric, items = bench_list(args)
     plan = bench._plan_of(items)
     stream = torch.cuda.current_stream(dev)
-    calls = {fmt: MxCall(items, fmt) for fmt in mx.FORMATS}
-    ones = {fmt: MxCall(items[:len(shapes)], fmt) for fmt in mx.FORMATS}
+    calls = {"mxfp8": MxCall(items, "mxfp8")}   # the largest codes: every format writes into its arenas
+    calls.update({fmt: MxCall(items, fmt, share=calls["mxfp8"]) for fmt in mx.FORMATS if fmt != "mxfp8"})
+    ones = {"mxfp8": MxCall(items[:len(shapes)], "mxfp8")}
+    ones.update({fmt: MxCall(items[:len(shapes)], fmt, share=ones["mxfp8"]) for fmt in mx.FORMATS if fmt != "mxfp8"})
     one_plan = bench._plan_of(items[:len(shapes)])
     legs = []
     for _ in range(3):
@@ -123,12 +143,46 @@ def timing(args):
                     "ratio_to_sweep_ms": round(ms / sweep_ms, 3), "table_bytes": c.ws_bytes,
                     "one_model_us": round(1e3 * timed(lambda: ones[fmt].run(stream), stream, args.warmup, args.steps), 2)}
     torch.cuda.synchronize()
-    emit([out], Path(args.out) if args.out else OUT / "mx_quantize_time.jsonl")
+    emit([out], Path(args.out) if args.out else OUT / "mx6_quantize_time.jsonl")
+
+
+def parent_ab(args):
+    """MXFP4 and MXFP8 on the bench list through two builds of the library in one
+    process: --ab's (the parent commit's, built into a scratch directory) and this
+    tree's, alternated three times, both on the same descriptor table, outputs and
+    workspace (where the buffers lie moves a call by more than the builds differ).  The
+    formats the other build lacks are not timed."""
+    dev, b, shapes, per_copy, copies, symmetric, items = bench_list(args)
+    stream = torch.cuda.current_stream(dev)
+    other = _lib.load(args.ab)
+    assert other is not _lib.load()   # (its kernel's code object loads in the first leg's warm-up)
+    fmts = ("mxfp4", "mxfp8")
+    calls = {fmt: MxCall(items, fmt) for fmt in fmts}
+    libs = {"parent": other, "new": _lib.load()}
+    legs = []
+    for _ in range(3):
+        leg = {}
+        for fmt in fmts:
+            for who in ("parent", "new"):
+                leg["%s_%s_ms" % (who, fmt)] = round(timed(lambda: calls[fmt].run(stream, libs[who]), stream, args.warmup,
+                                                           args.steps), 4)
+        legs.append(leg)
+    out = {"what": "dfq_mx_quantize_batch (dst + codes + scales + esum) on the bench headline list: the parent commit's "
+                   "library against this tree's, alternated in one process",
+           "device": torch.cuda.get_device_name(dev), "model": b.model, "copies": copies, "tensors": len(items),
+           "warmup": args.warmup, "steps": args.steps, "legs": legs}
+    for fmt in fmts:
+        old = [leg["parent_%s_ms" % fmt] for leg in legs]
+        new = [leg["new_%s_ms" % fmt] for leg in legs]
+        out[fmt] = {"parent_ms": old, "new_ms": new, "parent_min": min(old), "parent_max": max(old),
+                    "new_within_parent_spread": all(t <= max(old) for t in new)}
+    torch.cuda.synchronize()
+    emit([out], Path(args.out) if args.out else OUT / "mx6_parent_ab.jsonl")
 
 
 def quality_records(args):
     """Model SQNR of the zoo's MobileNetV2 (seed 0) from main_dfq --relu [--equalize
-    --absorption] --quantize --report: both MX formats beside per-channel symmetric
+    --absorption] --quantize --report: every MX format beside per-channel symmetric
     INT4 / INT8, with and without equalization.  One JSON line each: data, not
     assertions."""
     import tempfile
@@ -136,7 +190,7 @@ def quality_records(args):
     records = []
     with tempfile.TemporaryDirectory() as tmp:
         for equalize in (True, False):
-            for fmt, extra in (("mxfp4", []), ("mxfp8", []),
+            for fmt, extra in (("mxfp4", []), ("mxfp6_e3m2", []), ("mxfp6_e2m3", []), ("mxfp8", []),
                                ("int", ["--bits_weight", "4", "--granularity", "channel", "--symmetric"]),
                                ("int", ["--bits_weight", "8", "--granularity", "channel", "--symmetric"])):
                 path = Path(tmp) / "report.json"
@@ -149,7 +203,7 @@ def quality_records(args):
                                 "bits_per_weight": cfg.get("bits_per_weight", cfg["bits_weight"]), "equalize": equalize,
                                 "model_sqnr_db": round(m["sqnr_db"], 3), "worst_layer": m["worst_layer"],
                                 "worst_channel_sqnr_db": round(min(e["worst_channel_sqnr_db"] for e in rep["layers"]), 3)})
-    emit(records, Path(args.out) if args.out else OUT / "quality_mx.jsonl")
+    emit(records, Path(args.out) if args.out else OUT / "quality_mx6.jsonl")
 
 
 if __name__ == "__main__":
@@ -158,6 +212,7 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--quality", action="store_true")
-    ap.add_argument("--out", default=None, help="the JSON lines' file (default: under profiles/r09)")
+    ap.add_argument("--ab", default=None, help="another build of libdfq_hip.so to time MXFP4 / MXFP8 against")
+    ap.add_argument("--out", default=None, help="the JSON lines' file (default: under profiles/r10)")
     a = ap.parse_args()
-    quality_records(a) if a.quality else timing(a)
+    quality_records(a) if a.quality else parent_ab(a) if a.ab else timing(a)
