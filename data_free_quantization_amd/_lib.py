@@ -38,7 +38,7 @@ EXPORTS = [
     "dfq_act_moments", "dfq_act_minmax", "dfq_act_affine",
     "dfq_pair_stats_ws_bytes", "dfq_pair_stats_batch",
     "dfq_clip_search_ws_bytes", "dfq_clip_search_batch",
-    "dfq_mx_quantize_ws_bytes", "dfq_mx_quantize_batch",
+    "dfq_mx_quantize_ws_bytes", "dfq_mx_quantize_batch", "dfq_mx_gemm",
 ]
 #: entry points only the diagnostics library exports (include/dfq_diag.h)
 DIAG_EXPORTS = ["dfq_probe_stream", "dfq_probe_lds", "dfq_debug_timeline", "dfq_debug_ablate",
@@ -114,6 +114,15 @@ class MxDesc(C.Structure):
     _fields_ = [
         ("src", C.c_void_p), ("dst", C.c_void_p), ("codes", C.c_void_p), ("scales", C.c_void_p), ("esum", C.c_void_p),
         ("rows", C.c_int64), ("row_len", C.c_int64), ("khw", C.c_int32), ("format", C.c_int32), ("flags", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class MxGemmDesc(C.Structure):
+    _fields_ = [
+        ("a_codes", C.c_void_p), ("a_scales", C.c_void_p), ("b_codes", C.c_void_p), ("b_scales", C.c_void_p),
+        ("bias", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_int64), ("M", C.c_int64), ("N", C.c_int64),
+        ("K", C.c_int64), ("a_format", C.c_int32), ("b_format", C.c_int32), ("flags", C.c_int32),
         ("reserved", C.c_int32),
     ]
 
@@ -209,6 +218,7 @@ def load(path: Optional[os.PathLike] = None) -> C.CDLL:
         "dfq_clip_search_batch": ([C.POINTER(ClipSearchDesc), I32, P, I64, P], C.c_int),
         "dfq_mx_quantize_ws_bytes": ([C.POINTER(MxDesc), I32], C.c_int64),
         "dfq_mx_quantize_batch": ([C.POINTER(MxDesc), I32, P, I64, P], C.c_int),
+        "dfq_mx_gemm": ([C.POINTER(MxGemmDesc), P], C.c_int),
     }
     diag = {
         "dfq_probe_stream": ([P, P, P, P, I64, I32, P], C.c_int),

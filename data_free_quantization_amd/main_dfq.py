@@ -32,6 +32,12 @@ Same flags and stage order; the transforms run on the GPU.  Additive flags:
                        elements of a row; 4.25 / 6.25 / 6.25 / 8.25 bits per weight), to which
                        those three flags do not apply.  There is no bare mxfp6.  Not with --clip_search, --bc_mode reference,
                        --clip_weight under --bc_mode fused, or --world_size > 1
+  --mx_matmul {mxfp4,mxfp6_e2m3,mxfp6_e3m2,mxfp8}   run the evaluation's Linear and 1x1-convolution
+                       products on the scaled matrix instruction (utils.quantize.mx_matmul_forward,
+                       mx.mx_linear): the stored MX weight codes times the layer's input rounded
+                       to this MX format in blocks of 32 along the channel dimension -- a second
+                       rounding of the activations, after their integer fake quant.  Needs an MX
+                       --weight_format
 
 Example (README.md:137 of the reference):
   python -m data_free_quantization_amd.main_dfq --task cls --relu --equalize --absorption \
@@ -101,7 +107,12 @@ def get_argument(argv=None):
                    help="the narrowest candidate as a share of the min-max range, in [0, 1]")
     p.add_argument("--weight_format", default="int", choices=["int", "mxfp4", "mxfp6_e2m3", "mxfp6_e3m2", "mxfp8"],
                    help="weight codes: the integer grid, or OCP MX block-scaled FP4 / FP6 / FP8 (32-element blocks)")
+    p.add_argument("--mx_matmul", default=None, choices=["mxfp4", "mxfp6_e2m3", "mxfp6_e3m2", "mxfp8"],
+                   help="evaluate with the MX layers' products on the scaled matrix instruction, activations "
+                        "rounded to this MX format")
     args = p.parse_args(argv)
+    if args.mx_matmul is not None and args.weight_format == "int":
+        p.error("--mx_matmul needs an MX --weight_format")
     if args.weight_format != "int":
         if not args.quantize:
             p.error("--weight_format needs --quantize")
@@ -303,8 +314,10 @@ def main(argv=None):
         start = time.time()
         # the weights are final from here: the Quant* layers keep their weight /
         # bias fake-quant between batches (utils.quantize.frozen_weights)
-        from .utils.quantize import frozen_weights
-        with frozen_weights():
+        import contextlib
+        from .utils.quantize import frozen_weights, mx_matmul_forward
+        scope = mx_matmul_forward(args.mx_matmul) if args.mx_matmul is not None else contextlib.nullcontext()
+        with frozen_weights(), scope:
             accuracy = inference_all(model, args.task, args)
         print(f"Inference time is {time.time() - start} seconds")
         if args.quantize:

@@ -5,8 +5,11 @@ Host wrapper of ``dfq_mx_quantize_batch`` (include/dfq_hip.h): FP
 scale per 32 consecutive elements of a row, the operand format of CDNA4's scaled
 matrix instructions.  ``mx_quantize`` takes every tensor of a list in one C call (one
 launch, one HBM pass, asynchronous on the stream); ``mx_dequantize`` rebuilds the
-fp32 values from codes and scales in plain torch, exactly, on CPU or GPU.  There is
-no CPU fallback for the quantizer: CPU tensors raise."""
+fp32 values from codes and scales in plain torch, exactly, on CPU or GPU.
+``mx_gemm`` multiplies two operands given as codes and scales on the scaled matrix
+instruction (``dfq_mx_gemm``), ``mx_linear`` quantizes an fp32 input and
+weight and multiplies them.  There is no CPU fallback for the quantizer or the
+multiply: CPU tensors raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -135,6 +138,107 @@ def mx_quantize(items: Sequence[MXItem], stream: Optional[torch.cuda.Stream] = N
         for t in keep:
             t.record_stream(s)
     return items
+
+
+def _codes_arg(name: str, codes, scales, fmt: str, K: int):
+    """The checks of one mx_gemm operand; its row count."""
+    if fmt not in FORMATS:
+        raise ValueError("%s_fmt must be %s, got %r" % (name, _NAMES, fmt))
+    for what, t in ((name + "_codes", codes), (name + "_scales", scales)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(what + ": a uint8 tensor on the GPU")
+        if not t.is_cuda:
+            raise RuntimeError("data_free_quantization_amd multiplies MX codes on a ROCm GPU only; "
+                               "%s is on %s (there is no CPU fallback)" % (what, t.device))
+        if t.dtype != torch.uint8 or not t.is_contiguous():
+            raise TypeError(what + ": contiguous uint8 on the GPU")
+    nb, cb = blocks(K), FORMATS[fmt][2]
+    if scales.dim() != 2 or scales.shape[1] != nb or scales.shape[0] < 1:
+        raise ValueError("%s_scales must be [rows, %d] for K = %d, got %s" % (name, nb, K, tuple(scales.shape)))
+    rows = scales.shape[0]
+    if codes.numel() != rows * nb * cb:
+        raise ValueError("%s_codes holds %d bytes, [%d, %d, %d] needed" % (name, codes.numel(), rows, nb, cb))
+    if codes.data_ptr() % (8 if cb == 24 else 16):
+        raise ValueError("%s_codes must be %d-byte aligned" % (name, 8 if cb == 24 else 16))
+    return rows
+
+
+def mx_gemm(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor,
+            b_fmt: str, K: int, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+            stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """out[m, n] = sum_k A[m, k] * B[n, k] (+ bias[n]) on the scaled matrix instruction
+    (dfq_mx_gemm): A and B as the ``codes`` ([rows, nb, 16 | 24 | 32]
+    uint8) and ``scales`` ([rows, nb] uint8) ``mx_quantize`` writes for rows of K elements,
+    in any two formats.  ``out``: fp32 [M, N] whose rows may be strided (a column slice of
+    a wider tensor); allocated when None.  One launch, asynchronous on ``stream``."""
+    K = int(K)
+    if K < 1:
+        raise ValueError("K must be >= 1")
+    M = _codes_arg("a", a_codes, a_scales, a_fmt, K)
+    N = _codes_arg("b", b_codes, b_scales, b_fmt, K)
+    dev = a_codes.device
+    if bias is not None:
+        _lib.require_device(bias)
+        if bias.numel() != N:
+            raise ValueError("bias holds %d elements, %d needed" % (bias.numel(), N))
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=dev)
+    else:
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32:
+            raise TypeError("out: float32 on the GPU")
+        if out.dim() != 2 or tuple(out.shape) != (M, N) or out.stride(1) != 1 or (M > 1 and out.stride(0) < N):
+            raise ValueError("out must be [%d, %d] with unit column stride and a row stride >= %d" % (M, N, N))
+    for t in (a_scales, b_codes, b_scales, bias, out):
+        if t is not None and t.device != dev:
+            raise ValueError("every tensor of an mx_gemm call must live on one device")
+    d = _lib.MxGemmDesc()
+    d.a_codes, d.a_scales, d.b_codes, d.b_scales = (t.data_ptr() for t in (a_codes, a_scales, b_codes, b_scales))
+    d.bias = bias.data_ptr() if bias is not None else None
+    d.out, d.ldo = out.data_ptr(), (out.stride(0) if M > 1 else max(out.stride(0), N))
+    d.M, d.N, d.K, d.a_format, d.b_format = M, N, K, FORMATS[a_fmt][0], FORMATS[b_fmt][0]
+    s = C.c_void_p(stream.cuda_stream) if stream is not None else _lib.raw_stream(dev)
+    _lib.check(_lib.load().dfq_mx_gemm(C.byref(d), s), "dfq_mx_gemm", ValueError)
+    if stream is not None and stream != torch.cuda.current_stream(dev):
+        for t in (a_codes, a_scales, b_codes, b_scales, bias, out):
+            if t is not None:
+                t.record_stream(stream)
+    return out
+
+
+#: mx_linear calls since the last reset (utils.quantize.mx_matmul_forward resets it on entry)
+LINEAR_CALLS = 0
+
+
+def reset_linear_calls() -> None:
+    global LINEAR_CALLS
+    LINEAR_CALLS = 0
+
+
+def mx_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], weight_format: str,
+              act_format: str = "mxfp8", weight_mx=None) -> torch.Tensor:
+    """x @ weight.T (+ bias) on the scaled matrix instruction: x (fp32 [M, K], contiguous)
+    rounded to ``act_format`` and weight (fp32 [N, K]) to ``weight_format`` by
+    ``mx_quantize`` -- blocks of 32 along K for both, codes and scales only -- then one
+    ``mx_gemm``.  A weight that already lies on its MX grid (quantize_targ_layer's) re-quantizes
+    to its own codes, so the product is of exactly the stored values.
+    ``weight_mx``: the weight's (codes, scales) from an earlier call, instead of
+    quantizing it again.  Returns fp32 [M, N]."""
+    global LINEAR_CALLS
+    for fmt in (weight_format, act_format):
+        if fmt not in FORMATS:
+            raise ValueError("format must be %s, got %r" % (_NAMES, fmt))
+    _lib.require_device(x, weight, bias)
+    if x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1] or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError("x must be [M, K] and weight [N, K], got %s and %s" % (tuple(x.shape), tuple(weight.shape)))
+    xi = allocate(x.detach(), act_format, want_dst=False)
+    if weight_mx is None:
+        wi = allocate(weight.detach(), weight_format, want_dst=False)
+        mx_quantize([xi, wi])
+        weight_mx = (wi.codes, wi.scales)
+    else:
+        mx_quantize([xi])
+    LINEAR_CALLS += 1
+    return mx_gemm(xi.codes, xi.scales, act_format, weight_mx[0], weight_mx[1], weight_format, x.shape[1], bias=bias)
 
 
 def _tables(fmt: str, device) -> torch.Tensor:

@@ -361,9 +361,79 @@ def frozen_weights():
         _lib.weights_changed()
 
 
+_MX_MATMUL = None   # the activation format of the open mx_matmul_forward() scope
+
+
+@contextlib.contextmanager
+def mx_matmul_forward(act_format: str = "mxfp8"):
+    """Inference with the MX layers' products on the scaled matrix instruction: inside
+    this scope a Quant* layer whose ``weight_format`` mark (quantize_targ_layer's) is an MX
+    format multiplies through ``mx.mx_linear`` -- its weight's MX codes times its input
+    rounded to ``act_format`` in blocks of 32 along the channel dimension -- instead of
+    ``F.linear`` / ``F.conv2d`` on fp32.  Eligible: QuantLinear / QLinear, and QuantConv2d /
+    QConv2d with a 1x1 kernel, groups == 1 and zero padding (a stride slices the input).
+    The activation and bias fake quant stay; every other layer, and everything outside the
+    scope, is untouched.  The scope resets ``mx.LINEAR_CALLS``.  Inside ``frozen_weights()``
+    a layer's weight codes are kept under the weight cache's key."""
+    from .. import mx
+    if act_format not in mx.FORMATS:
+        raise ValueError("act_format must be an MX format name, got %r" % (act_format,))
+    global _MX_MATMUL
+    prev, _MX_MATMUL = _MX_MATMUL, act_format
+    mx.reset_linear_calls()
+    try:
+        yield
+    finally:
+        _MX_MATMUL = prev
+
+
 class _QuantWeightMixin:
     """Forward of the Quant* layers: activation fake-quant, per-tensor weight
     fake-quant with float(min)/float(max), bias fake-quant with the data range."""
+
+    def _weight_key(self, weight, bias):
+        """The weight cache's key inside frozen_weights() for the module's own parameters, else None."""
+        if not (_FROZEN > 0 and weight is self.weight and bias is self.bias):
+            return None
+        return (weight.data_ptr(), weight._version, self.num_bits, _lib.WEIGHT_GENERATION,
+                None if bias is None else (bias.data_ptr(), bias._version), self.num_bits_bias)
+
+    def _mx_format(self):
+        """The layer's MX weight format when its product runs through mx.mx_linear, else None."""
+        fmt = self.__dict__.get("weight_format", "int")
+        if _MX_MATMUL is None or fmt == "int":
+            return None
+        if isinstance(self, nn.Conv2d) and not (tuple(self.kernel_size) == (1, 1) and self.groups == 1 and
+                                                 tuple(self.padding) == (0, 0)):
+            return None
+        return fmt
+
+    def _mx_product(self, x2d, weight, bias, qweight, qbias, fmt):
+        """mx.mx_linear of the [rows, K] input with the layer's weight (its codes kept in frozen_weights())."""
+        from .. import mx
+        if not _no_autograd(x2d, weight, bias):
+            raise RuntimeError("mx_matmul_forward is an inference path: run it under torch.no_grad()")
+        w2d = qweight.reshape(qweight.shape[0], -1)
+        key = self._weight_key(weight, bias)
+        if key is None:
+            self.__dict__.pop("_mx_w_cache", None)
+            return mx.mx_linear(x2d, w2d, qbias, fmt, _MX_MATMUL)
+        hit = self.__dict__.get("_mx_w_cache")
+        if hit is None or hit[0] != (key, fmt):
+            wi = mx.mx_quantize([mx.allocate(w2d.detach().contiguous(), fmt, want_dst=False)])[0]
+            hit = self.__dict__["_mx_w_cache"] = ((key, fmt), wi.codes, wi.scales)
+        return mx.mx_linear(x2d, w2d, qbias, fmt, _MX_MATMUL, weight_mx=(hit[1], hit[2]))
+
+    def _mx_conv1x1(self, input, weight, bias, qweight, qbias, fmt):
+        x = input[:, :, ::self.stride[0], ::self.stride[1]]
+        n, c, h, w = x.shape
+        x2d = x.permute(0, 2, 3, 1).contiguous().view(n * h * w, c)   # channels last: a row per pixel
+        y = self._mx_product(x2d, weight, bias, qweight, qbias, fmt)
+        return y.view(n, h, w, -1).permute(0, 3, 1, 2).contiguous()
+
+    def _mx_linear(self, input, weight, bias, qweight, qbias, fmt):
+        x2d = input.reshape(-1, input.shape[-1]).contiguous()
+        return self._mx_product(x2d, weight, bias, qweight, qbias, fmt).view(*input.shape[:-1], -1)
 
     def _qparams(self, weight, bias):
         # a layer quantize_targ_layer left in an MX format (weight_format="mxfp4" / "mxfp8") holds
@@ -377,10 +447,9 @@ class _QuantWeightMixin:
             # never cached: its id and address are reused), their torch version
             # counters, and the DFQ transforms' generation (_lib.WEIGHT_GENERATION:
             # they write through the library, past the version counters).
-            cacheable = _FROZEN > 0 and weight is self.weight and bias is self.bias
+            key = self._weight_key(weight, bias)
+            cacheable = key is not None
             if cacheable:
-                key = (weight.data_ptr(), weight._version, self.num_bits, _lib.WEIGHT_GENERATION,
-                       None if bias is None else (bias.data_ptr(), bias._version), self.num_bits_bias)
                 hit = self.__dict__.get("_qw_cache")
                 if hit is not None and hit[0] == key:
                     return hit[1], hit[2]
@@ -419,6 +488,9 @@ class QuantConv2d(_QuantWeightMixin, nn.Conv2d):
     def forward(self, input):
         input = self.quant(input)
         qweight, qbias = self._qparams(self.weight, self.bias)
+        fmt = self._mx_format()
+        if fmt is not None:
+            return self._mx_conv1x1(input, self.weight, self.bias, qweight, qbias, fmt)
         return F.conv2d(input, qweight, qbias, self.stride, self.padding, self.dilation, self.groups)
 
 
@@ -448,6 +520,9 @@ class QuantLinear(_QuantWeightMixin, nn.Linear):
     def forward(self, input):
         input = self.quant(input)
         qweight, qbias = self._qparams(self.weight, self.bias)
+        fmt = self._mx_format()
+        if fmt is not None:
+            return self._mx_linear(input, self.weight, self.bias, qweight, qbias, fmt)
         return F.linear(input, qweight, qbias)
 
 
@@ -500,6 +575,9 @@ class QConv2d(QuantConv2d):
         input = self.quant(input)
         w, b = self._scaled()
         qweight, qbias = self._qparams(w, b)
+        fmt = self._mx_format()
+        if fmt is not None:
+            return self._mx_conv1x1(input, w, b, qweight, qbias, fmt)
         return F.conv2d(input, qweight, qbias, self.stride, self.padding, self.dilation, self.groups)
 
 
@@ -537,6 +615,9 @@ class QLinear(QuantLinear):
         input = self.quant(input)
         w, b = self._scaled()
         qweight, qbias = self._qparams(w, b)
+        fmt = self._mx_format()
+        if fmt is not None:
+            return self._mx_linear(input, w, b, qweight, qbias, fmt)
         return F.linear(input, qweight, qbias)
 
 

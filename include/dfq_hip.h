@@ -490,6 +490,52 @@ int64_t dfq_mx_quantize_ws_bytes(const dfq_mx_desc* descs, int32_t n);
  * same results.  Each tensor at most once per call.  n == 0: DFQ_OK, nothing launched. */
 int dfq_mx_quantize_batch(const dfq_mx_desc* descs, int32_t n, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- MX matrix multiply on the scaled matrix instruction (no reference counterpart) ----
+ * out[m][n] = sum_k A[m][k] * B[n][k] (+ bias[n]), A and B given as MX codes and scale
+ * bytes in exactly the layouts dfq_mx_quantize_batch writes (both operands K-contiguous,
+ * nb = ceil(K / 32) blocks per row, cb = 16 / 24 / 32 code bytes per block, the padding of
+ * a partial last block +0 codes), each in any of the four formats.  The product runs on
+ * v_mfma_scale_f32_16x16x128_f8f6f4, which reads the stored code bytes and scale bytes
+ * as they are: no dequantized operand is ever written to memory.
+ * Numerics: with a_mk, b_nk the values the codes stand for (y = +-q * 2^(scale - 127)),
+ * every product a*b has at most 8 significant bits and is exact in fp32.  Domain: scale
+ * bytes with |X_a + X_b| <= 100 (X = scale - 127) for every pair of blocks that meet, so
+ * nothing leaves the normal range; an all-zero block (scale byte 0, +0 codes)
+ * contributes 0.  The instruction's summation order and internal width are not
+ * specified, so the contract is a bound, |acc - sum a*b| <= c(nb) * sum |a*b|:
+ *   c = 32 * nb * 2^-24, which any-order fp32 accumulation of the exact products meets
+ *       and the hardware was measured to meet at nb = 13 and 40 (worst 0.17 of it);
+ *   c = 6.4e-5 for nb <= 4 (one K step): with an FP8 operand the instruction's own error,
+ *       about 2^-13 of the step's largest product whatever K, was measured at up to
+ *       3.2e-5 * sum |a*b| (K = 24), above the derived bound; twice that is documented.
+ * Where every partial sum in any order is exact in fp32 (integer-like data) the result is
+ * exact; products of FP6 / FP4 operands alone were exact in every measurement (DESIGN.md
+ * 3.8).  The bias is one fp32 add after the accumulation.  An element's result is the same bits from run to run
+ * and does not depend on ldo, on the addresses or on other calls: one lane's accumulator
+ * in K order, no atomics, no split of K.
+ * Asynchronous on `stream`, no host wait, no workspace.  Checked on the host before any
+ * device call: DFQ_ERR_INVALID for a NULL operand, scale or out pointer, an unknown
+ * format, M, N or K < 1 (or beyond 2^31 rows / 2^40 columns), non-zero flags or
+ * reserved, a code base not 16-B aligned (FP6: 8-B), out or bias not 4-B aligned;
+ * DFQ_ERR_SHAPE for ldo < N.  There is no slow path for misaligned bases. */
+typedef struct dfq_mx_gemm_desc {
+    const void*  a_codes;   /* uint8 [M, nb, cb(a_format)] */
+    const void*  a_scales;  /* uint8 [M, nb] */
+    const void*  b_codes;   /* uint8 [N, nb, cb(b_format)] */
+    const void*  b_scales;  /* uint8 [N, nb] */
+    const float* bias;      /* [N] or NULL */
+    float*       out;       /* [M, N] fp32, row stride ldo */
+    int64_t      ldo;       /* >= N */
+    int64_t      M;
+    int64_t      N;
+    int64_t      K;         /* nb = ceil(K / 32) */
+    int32_t      a_format;  /* DFQ_MX_* as in dfq_mx_desc */
+    int32_t      b_format;
+    int32_t      flags;     /* 0 */
+    int32_t      reserved;  /* 0 */
+} dfq_mx_gemm_desc;
+int dfq_mx_gemm(const dfq_mx_gemm_desc* d, void* stream);
+
 /* ---- high-bias absorption (bias_absorption.py:147-197) ------------------
  * c = max(bn_b - N*bn_w, 0) (bn_* = the BN's fake_weight / fake_bias);
  * b2[o] += sum_i (sum_k W2[o,i,k]) * c[g*i2 + i];  b1 -= c;  bn_b -= c.
