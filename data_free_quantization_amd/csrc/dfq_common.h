@@ -431,6 +431,33 @@ __device__ inline float wave_inner_sum(Get get, int64_t n, int lane) {
     return fa;
 }
 
+// A contiguous reduction of n elements to ONE output by one wave (x.sum(),
+// x.view(-1, 1).sum(0): TensorIterator collapses both to the same loop).  Below
+// 32768 elements or with one thread it is the serial aten_inner_sum; otherwise
+// two_pass_reduction: min(threads, ceil(n / 32768)) chunks of ceil(n / chunks)
+// elements, each an inner sum into its slot of a zeroed buffer of `threads`
+// slots, then the inner sum of the buffer (as dfq_cle's stop metric).  slots:
+// this wave's LDS scratch, >= threads floats.
+template <typename Get>
+__device__ inline float wave_full_sum(Get get, int64_t n, int threads, int lane, float* slots) {
+    int64_t nt = 1;
+    if (n >= 32768 && threads > 1) nt = ceil_div(n, (int64_t)32768) < threads ? ceil_div(n, (int64_t)32768) : threads;
+    if (nt == 1) return wave_inner_sum(get, n, lane);
+    const int64_t chunk = ceil_div(n, nt);
+    for (int t = lane; t < threads; t += 64) slots[t] = 0.f;
+    wave_lds_sync();
+    for (int64_t t = 0; t < nt && t * chunk < n; ++t) {
+        const int64_t b0 = t * chunk, len = (b0 + chunk < n ? b0 + chunk : n) - b0;
+        const float s = wave_inner_sum([&](int64_t i) { return get(b0 + i); }, len, lane);
+        if (lane == 0) slots[t] = s;
+    }
+    wave_lds_sync();
+    float r = 0.f;
+    if (lane == 0) r = aten_inner_sum([&](int64_t t) { return slots[t]; }, (int64_t)threads);
+    wave_lds_sync();   // the scratch is reused by the caller
+    return __shfl(r, 0, 64);
+}
+
 // Agent-coherent fp32 store / load (sc1: no stale copy in another XCD's L2), for
 // the words one block hands to another inside a launch (CLE: level-1 sums, chunk
 // tails, chunk sums; the BC chain: every vector a later phase reads) without an
@@ -456,7 +483,8 @@ __device__ __forceinline__ float ld_coh(const DFQ_GLOBAL float* p) {
 }
 
 // Which reduction aten_outer_col_sum uses for column c: true = the 32-column
-// multi_row_sum cascade, false = row_sum (ILP 4).
+// multi_row_sum cascade, false = row_sum (ILP 4).  F >= 2: a single column is a
+// contiguous reduction (wave_full_sum).
 __host__ __device__ inline bool aten_outer_col_is_cascade(int64_t R, int64_t F, int64_t c, int threads) {
     int64_t c0 = 0, c1 = F;
     if (R * F >= 32768 && threads > 1) {

@@ -182,7 +182,9 @@ bc_propagate_kernel(const float* __restrict__ bias_vec, int64_t nrows, int64_t f
     const int64_t nwaves = (int64_t)gridDim.x * (kThreads / 64);
     for (int64_t c = wave; c < f; c += nwaves) {
         auto get = [&](int64_t r) { return bias_vec[r * f + c]; };
-        const float sum = aten_outer_col_is_cascade(nrows, f, c, threads)
+        // one column is no outer reduction: view(-1, 1).mean(0) is the contiguous sum
+        const float sum = f == 1 ? wave_full_sum(get, nrows, threads, lane, b0s)
+                          : aten_outer_col_is_cascade(nrows, f, c, threads)
                               ? wave_cascade(get, nrows, lane, b0s, b1s, kBcScratch)
                               : wave_row_sum(get, nrows, lane, b0s, b1s, kBcScratch);
         if (lane == 0) fake_b[c] = fake_b[c] + (-sum) / (float)nrows;   // sum(-v) == -sum(v) exactly
@@ -275,8 +277,10 @@ __global__ void __launch_bounds__(kThreads) bc_layer_kernel(BcLayerJob J) {
         for (int64_t r = lane; r < J.nrows; r += 64) colv[r] = get(r);   // nrows <= kBcStage (bc_layer_group)
         wave_lds_sync();
         auto lds = [&](int64_t r) { return colv[r]; };
-        const float sum = cascade ? wave_cascade(lds, J.nrows, lane, b0s, b1s, kBcScratch)
-                                  : wave_row_sum(lds, J.nrows, lane, b0s, b1s, kBcScratch);
+        // (one column: the contiguous sum, serial at nrows <= kBcStage < 32768)
+        const float sum = J.F == 1 ? wave_inner_sum(lds, J.nrows, lane)
+                          : cascade ? wave_cascade(lds, J.nrows, lane, b0s, b1s, kBcScratch)
+                                    : wave_row_sum(lds, J.nrows, lane, b0s, b1s, kBcScratch);
         wave_lds_sync();   // colv is rewritten by the next column
         if (lane == 0) J.fake_b[c] = J.fake_b[c] + (-sum) / (float)J.nrows;
     }
@@ -943,7 +947,8 @@ extern "C" int dfq_bias_absorb(const float* w2, float* b1, float* b2, float* bn_
     const int64_t groups = c1 / i2;   // bias_absorption.py:159
     if (groups <= 0 || o2 % groups != 0) return DFQ_ERR_SHAPE;
     const int64_t o2g = o2 / groups;
-    if (groups * i2 > c1) return DFQ_ERR_SHAPE;
+    // c[start_inner:end_inner] has c1 // groups elements (:44,:66): matmul raises unless that is i2
+    if (c1 / groups != i2) return DFQ_ERR_SHAPE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int wave_blocks = (int)std::min<int64_t>(ceil_div(o2, kThreads / 64), 2048);
     hipLaunchKernelGGL(absorb_gemv_kernel, dim3(wave_blocks), dim3(kThreads), 0, s, w2, b2, bn_w, bn_b, o2, i2, khw2,
@@ -1057,7 +1062,7 @@ static int absorb_tables(const dfq_absorb_desc* d, int32_t n, AbsTables& T, int3
         if (!x.w2 || !x.b1 || !x.b2 || !x.bn_w || !x.bn_b || x.c1 <= 0 || x.o2 <= 0 || x.i2 <= 0 || x.khw2 <= 0)
             return DFQ_ERR_INVALID;
         const int64_t groups = x.c1 / x.i2;   // bias_absorption.py:159
-        if (groups <= 0 || x.o2 % groups != 0 || groups * x.i2 > x.c1) return DFQ_ERR_SHAPE;
+        if (groups <= 0 || x.o2 % groups != 0 || x.c1 / groups != x.i2) return DFQ_ERR_SHAPE;   // as dfq_bias_absorb
         if (x.b1 == x.b2) return DFQ_ERR_SHAPE;
         for (int32_t q = 0; q < r; ++q)   // a BN shared by two relations: the per-relation call keeps its order
             if (d[q].bn_b == x.bn_b) return DFQ_ERR_UNSUPPORTED;
@@ -1176,6 +1181,7 @@ extern "C" int dfq_bc_propagate(const float* bias_vec, int64_t numel, float* fak
                                 void* stream) {
     if (!bias_vec || !fake_b || numel <= 0 || f <= 0 || ref_threads < 1) return DFQ_ERR_INVALID;
     if (numel % f != 0) return DFQ_ERR_SHAPE;   // .view(-1, F) fails
+    if (f == 1 && ref_threads > kBcScratch) return DFQ_ERR_UNSUPPORTED;   // wave_full_sum's slots
     hipLaunchKernelGGL(bc_propagate_kernel, dim3((int)std::min<int64_t>(ceil_div(f, (int64_t)4), 2048)), dim3(kThreads),
                        0, static_cast<hipStream_t>(stream),
                        bias_vec, numel / f, f, (int)ref_threads, fake_b);
@@ -1313,6 +1319,7 @@ extern "C" int dfq_bc_chain(const dfq_bc_op* ops, int32_t n_ops, int32_t* failed
             case DFQ_BC_OP_PROPAGATE:
                 if (!op.a || !op.out || op.n <= 0 || op.f <= 0 || op.flag < 1) return fail(k, DFQ_ERR_INVALID);
                 if (op.n % op.f != 0) return fail(k, DFQ_ERR_SHAPE);
+                if (op.f == 1 && op.flag > kBcScratch) return fail(k, DFQ_ERR_UNSUPPORTED);
                 break;
             case DFQ_BC_OP_COPY:
                 if (!op.a || !op.out || op.n < 0) return fail(k, DFQ_ERR_INVALID);

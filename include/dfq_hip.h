@@ -539,7 +539,10 @@ int dfq_mx_gemm(const dfq_mx_gemm_desc* d, void* stream);
 /* ---- high-bias absorption (bias_absorption.py:147-197) ------------------
  * c = max(bn_b - N*bn_w, 0) (bn_* = the BN's fake_weight / fake_bias);
  * b2[o] += sum_i (sum_k W2[o,i,k]) * c[g*i2 + i];  b1 -= c;  bn_b -= c.
- * W2 is [o2, i2, khw2], c1 = W1.shape[0], groups = c1 / i2. */
+ * W2 is [o2, i2, khw2], c1 = W1.shape[0], groups = c1 / i2.
+ * DFQ_ERR_SHAPE (nothing written): groups must divide o2, and c1 / groups must be
+ * i2, as the reference's matmul demands (c1 = 10, i2 = 4 is refused; c1 = 9,
+ * i2 = 4 runs, its ninth channel in no group). */
 int dfq_bias_absorb(const float* w2, float* b1, float* b2, float* bn_w, float* bn_b,
                     int64_t c1, int64_t o2, int64_t i2, int64_t khw2, float n_sigma,
                     void* stream);
@@ -572,13 +575,17 @@ int dfq_bc_expect(const float* fake_w, const float* fake_b, int64_t n, int32_t r
  * broadcast shape [o, bcols]; bias[o] += mean_j bias_vec[o,j] (ATen's sum order)
  * (_compute_final_bias_correction + _apply_bias_correction, :61-106).
  * bias_vec (may be NULL) keeps the [o*bcols] vector for dfq_bc_propagate.
+ * A row's order does not depend on the reference's thread count, except for a
+ * single row (o == 1) of >= 32768 values, which follows the one-thread order.
  * Returns DFQ_ERR_SHAPE where torch would raise (non-broadcastable, or numel == o). */
 int dfq_bc_apply(const float* E, int64_t o, int64_t i2, const float* expect, int64_t f,
                  float* bias, float* bias_vec, int64_t* bcols_out, void* stream);
 /* dfq_bc_propagate: fake_b[c] += mean_r ( -bias_vec[r*f + c] ), r < numel/f
  * (bias_prev.view(-1, F).mean(0), bias_correction.py:206-213,251).  The fp32 sums
  * follow ATen's CPU reduction order for `ref_threads` intra-op threads (the
- * reference's torch.get_num_threads()). */
+ * reference's torch.get_num_threads()).  f == 1 is the contiguous
+ * sum (-v).mean() -- serial, or two passes over ref_threads from 32768 elements on;
+ * ref_threads above 1024 is DFQ_ERR_UNSUPPORTED there. */
 int dfq_bc_propagate(const float* bias_vec, int64_t numel, float* fake_b, int64_t f,
                      int32_t ref_threads, void* stream);
 

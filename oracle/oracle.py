@@ -40,7 +40,7 @@ def lib():
         L.oracle_cle_relation.argtypes = [P, P, P, P, P, I64, I64, I64, I64, I64, F64, F64, I32, F32, P]
         L.oracle_bias_absorb.argtypes = [P, P, P, P, P, I64, I64, I64, I64, F32]
         L.oracle_bc_expect.argtypes = [P, P, I64, I32, I32, P]
-        L.oracle_bc_apply.argtypes = [P, I64, I64, P, I64, P, P, C.POINTER(I64)]
+        L.oracle_bc_apply.argtypes = [P, I64, I64, P, I64, P, P, C.POINTER(I64), I32]
         L.oracle_bc_propagate.argtypes = [P, I64, P, I64, I32]
         L.oracle_mean_abs_diff.argtypes = [P, P, I64, I32]
         L.oracle_mean_abs_diff.restype = C.c_float
@@ -142,7 +142,9 @@ def bc_expect(w, b, relu, out=None):
     return out
 
 
-def bc_apply(E, expect, bias):
+def bc_apply(E, expect, bias, threads=1):
+    """``threads`` matters for a single output row of >= 32768 values only (ATen splits
+    every other shape over its rows)."""
     E, expect = _f32(E), _f32(expect)
     bias = _f32(bias).copy()
     o, i2 = E.shape[0], E.size // E.shape[0]
@@ -150,7 +152,7 @@ def bc_apply(E, expect, bias):
     f = expect.size
     bc_guess = i2 if (i2 == f or f == 1) else f
     vec = np.empty(o * bc_guess, np.float32)
-    rc = lib().oracle_bc_apply(_p(E), o, i2, _p(expect), f, _p(bias), _p(vec), C.byref(bcols))
+    rc = lib().oracle_bc_apply(_p(E), o, i2, _p(expect), f, _p(bias), _p(vec), C.byref(bcols), threads)
     if rc:
         raise ValueError(f"oracle_bc_apply rc={rc}")
     return bias, vec[: o * bcols.value]

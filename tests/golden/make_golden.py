@@ -13,6 +13,8 @@ Outputs (all plain arrays, loadable with numpy allow_pickle=False):
                       data range, utils/quantize.py:25-37)
   transform_cases.npz merge_batchnorm, _layer_equalization, bias_absorption,
                       bias_correction helpers on small layers
+  bc_edge_cases.npz   the bias-correction helpers at the HIP kernels' reduction edges
+                      (cases and inputs: tests/bc_edge_cases.py; section ``bc_edge``)
   pipeline_<model>.npz  main_dfq stage order on the synthetic models of
                       data_free_quantization_amd.zoo (positional graph keys)
 The synthetic model weights come from zoo.init_synthetic (numpy PCG64), so the
@@ -348,6 +350,81 @@ def transform_cases():
     A["meta"] = np.array(json.dumps(meta))
     np.savez_compressed(OUT / "transform_cases.npz", **A)
     print("transform cases:", len(meta))
+
+
+def bc_edge_cases():
+    """The bias-correction helpers at the reduction edges of the HIP kernels
+    (tests/bc_edge_cases.py: shapes, seeds, input builder) -> bc_edge_cases.npz.
+    Outputs only, as flat arrays in case order, plus one digest per case of its
+    inputs.  Results that ATen's thread split can change are taken at every thread
+    count of the case list; every other case is checked to be the same at all of
+    them and stored once."""
+    from tests import bc_edge_cases as BE
+
+    class _L:  # noqa: N801
+        pass
+
+    cm = lambda weight, bias: weight * torch.from_numpy(ref_bc.norm(0, 1).pdf(-bias / weight)).float() + \
+        bias * (1 - torch.from_numpy(ref_bc.norm.cdf(-bias / weight)).float())   # bias_correction.py:170-172
+    A, digests = {}, []
+
+    def at_threads(fn, threaded, what):
+        res = []
+        for t in BE.THREADS:
+            torch.set_num_threads(t)
+            res.append(fn())
+        torch.set_num_threads(8)
+        if threaded:
+            return np.stack(res).ravel()
+        assert all(r.tobytes() == res[0].tobytes() for r in res), f"{what}: depends on the thread count"
+        return res[0]
+
+    out = []
+    for c in BE.APPLY_CASES:
+        E, expect, bias = c.inputs()
+        digests.append(h(np.concatenate([E.ravel(), expect, bias])))
+
+        def run():
+            layer = _L()
+            layer.bias = nn.Parameter(torch.from_numpy(bias.copy()), requires_grad=False)
+            bv = ref_bc._compute_final_bias_correction(torch.from_numpy(E.copy()), ("one", torch.from_numpy(expect.copy())))
+            assert tuple(bv.shape) == (c.o, c.bcols)
+            ref_bc._apply_bias_correction(layer, bv)
+            return t2n(layer.bias)
+        out.append(at_threads(run, c.threaded, c.name))
+    A["apply_bias_out"] = np.concatenate(out)
+
+    out = []
+    for c in BE.PROP_CASES:
+        vec, fb = c.inputs()
+        digests.append(h(np.concatenate([vec, fb])))
+
+        def run():
+            prev = -torch.from_numpy(vec.copy())             # bias_prev = -bias (:251)
+            fbt = torch.from_numpy(fb.copy())
+            if prev.numel() != c.F:                          # :206-213
+                prev = prev.view(-1, c.F).mean(dim=0)
+            fbt.add_(prev)
+            return t2n(fbt)
+        out.append(at_threads(run, c.threaded, c.name))
+    A["prop_fb_out"] = np.concatenate(out)
+
+    out = []
+    for case in BE.EXPECT_CASES:
+        branch = []
+        for w, b, relu in BE.expect_terms(case):
+            layer = _L()
+            layer.fake_weight, layer.fake_bias = torch.from_numpy(w.copy()), torch.from_numpy(b.copy())
+            branch.append((layer, relu, "add"))
+        res = ref_bc._calculate_bias_correction_for_branches({"0": branch}, cm)
+        out.append(t2n(res["0"][1]))
+    w, b = BE.expect_inputs()
+    digests.append(h(np.concatenate([w, b])))
+    A["expect"] = np.concatenate(out)
+    A["digests"] = np.array(digests)
+    np.savez_compressed(OUT / "bc_edge_cases.npz", **A)
+    print("bc edge cases:", len(BE.APPLY_CASES), "apply,", len(BE.PROP_CASES), "propagate,", len(BE.EXPECT_CASES),
+          "expect")
 
 
 # ---------------------------------------------------------------------------
@@ -758,6 +835,8 @@ if __name__ == "__main__":
         chunk_cases()
     if "transform" in which:
         transform_cases()
+    if "bc_edge" in which:
+        bc_edge_cases()
     for m in ("mobilenetv2", "resnet50", "deeplab", "resnet18"):
         if m in which:
             pipeline(m, per_channel=(m == "mobilenetv2"))

@@ -1,6 +1,7 @@
 """Shared test helpers: golden fixture access and mode names."""
 import hashlib
 import json
+from functools import lru_cache
 from pathlib import Path
 
 import numpy as np
@@ -55,6 +56,38 @@ def case_flags(case):
 def transform_cases():
     z = np.load(GOLDEN / "transform_cases.npz", allow_pickle=False)
     return z, json.loads(str(z["meta"]))
+
+
+@lru_cache(maxsize=1)
+def bc_edge():
+    """tests/golden/bc_edge_cases.npz cut by the case lists of tests/bc_edge_cases.py:
+    {"apply": {name: {threads: bias_out}}, "prop": {name: {threads: fb_out}},
+    "expect": {name: vector}, "digest": {name: hex}} (read-only arrays; a result
+    that does not depend on the thread count is the same array under every count)."""
+    from tests import bc_edge_cases as BE
+    z = np.load(GOLDEN / "bc_edge_cases.npz", allow_pickle=False)
+
+    def cut(flat, cases, width):
+        out, at = {}, 0
+        for c in cases:
+            n = width(c)
+            rows = flat[at:at + n * (len(BE.THREADS) if c.threaded else 1)].reshape(-1, n)
+            at += rows.size
+            out[c.name] = {t: rows[k if c.threaded else 0] for k, t in enumerate(BE.THREADS)}
+        assert at == flat.size
+        return out
+
+    flat = {k: z[k] for k in ("apply_bias_out", "prop_fb_out", "expect")}
+    for a in flat.values():
+        a.setflags(write=False)
+    ex = flat["expect"].reshape(len(BE.EXPECT_CASES), BE.EXPECT_N)
+    names = [c.name for c in BE.APPLY_CASES] + [c.name for c in BE.PROP_CASES] + ["expect"]
+    digests = [str(d) for d in z["digests"]]
+    assert len(names) == len(digests)
+    return {"apply": cut(flat["apply_bias_out"], BE.APPLY_CASES, lambda c: c.o),
+            "prop": cut(flat["prop_fb_out"], BE.PROP_CASES, lambda c: c.F),
+            "expect": {case[0]: ex[k] for k, case in enumerate(BE.EXPECT_CASES)},
+            "digest": dict(zip(names, digests))}
 
 
 def pipeline(name, threads=8, bits_weight=8):

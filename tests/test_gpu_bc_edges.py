@@ -1,0 +1,235 @@
+"""The bias-correction kernels (csrc/dfq_transform.hip) against the REFERENCE's own
+results at the shapes where their reduction orders change
+(tests/golden/bc_edge_cases.npz, cases in tests/bc_edge_cases.py): bit for bit.
+
+Every fixture case runs twice: through the per-op entry points (dfq_bc_expect,
+dfq_bc_apply, dfq_bc_propagate: bc_expect_kernel / bc_apply_kernel /
+bc_propagate_kernel) and as one dfq_bc_chain group EXPECT+ -> APPLY
+(-> PROPAGATE), which runs as ONE bc_layer_kernel launch when the group is inside
+that kernel's limits and as the per-op kernels otherwise.  The groups are built
+so that the fixture's inputs are the group's values exactly:
+
+  * an APPLY case's expectation vector comes from a non-ReLU EXPECT term whose
+    fake_bias is the vector (such a term's expectation is its bias);
+  * a PROPAGATE case's vector is the bias_vec of an APPLY with E = the vector and
+    a one-element expectation of +0 (x + 0 == x; the builder makes no -0).  The
+    one-launch kernel recomputes fl(E + expect) in its propagate blocks, so this
+    also checks that recomputation's index math;
+  * an EXPECT case's terms accumulate into one slot that an APPLY then reads.
+    The expectation is elementwise, so a prefix of the fixture's vector is the
+    reference for a prefix of the inputs: f = 2048 is the longest the one-launch
+    kernel takes (an expectation of f > 1 values makes rows of f values, and rows
+    stop at kBcStage = 2048, before kBcMaxExpect = 4096 can), f = 4096 / 4097
+    straddle kBcMaxExpect in the group's own test of it.
+
+Which limit a case sits at is in its id (tests/bc_edge_cases.py names them):
+bcols 2048 / 2049 (row2048, row2049), nrows 2048 / 2049 (R2048_*, R2049_*),
+terms 8 / 9 (sum8, sum9), f 4096 / 4097.
+
+dfq_bc_apply has no reference thread count.  The reference's result depends on
+it for one shape only, a single output row of >= 32768 values (o == 1), where
+TensorIterator takes two passes split by thread; the kernel follows the
+one-thread order there and is held to the fixture's one-thread row
+(DESIGN.md 3.3).
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from data_free_quantization_amd import _lib
+from oracle import oracle as O
+from tests import bc_edge_cases as BE
+from tests.helpers import bc_edge
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+_OP = np.dtype([("kind", "<i4"), ("flag", "<i4"), ("a", "<u8"), ("b", "<u8"), ("out", "<u8"), ("out2", "<u8"),
+                ("n", "<i8"), ("i2", "<i8"), ("f", "<i8")])
+
+
+def T(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def N(t):
+    return t.cpu().numpy()
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _chain(rows):
+    arr = np.array(rows, dtype=_OP)
+    failed = C.c_int32(-1)
+    rc = _lib.load().dfq_bc_chain(arr.ctypes.data_as(C.POINTER(_lib.BcOp)), len(rows), C.byref(failed), _stream())
+    torch.cuda.synchronize()
+    _lib.check(rc, f"dfq_bc_chain (op {failed.value})")
+
+
+def _expect_op(w, b, out, relu, accumulate):
+    return (_lib.DFQ_BC_OP_EXPECT, int(relu) | (int(accumulate) << 1), w.data_ptr(), b.data_ptr(), out.data_ptr(), 0,
+            b.numel(), 0, 0)
+
+
+def _apply_op(E, expect, bias, vec, o, i2, f):
+    return (_lib.DFQ_BC_OP_APPLY, 0, E.data_ptr(), expect.data_ptr(), bias.data_ptr(), vec.data_ptr(), o, i2, f)
+
+
+def _same_bits(got, want, what=""):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    bad = np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))
+    # (+0 and -0 compare equal below, as the fixtures' digests fold them)
+    bad = bad[got.ravel()[bad] != want.ravel()[bad]] if bad.size else bad
+    assert bad.size == 0, f"{what}: {bad.size} of {got.size} differ, first at {bad[:5]}: " \
+                          f"{got.ravel()[bad[:5]]} vs {want.ravel()[bad[:5]]}"
+
+
+# ---- APPLY ----------------------------------------------------------------
+@pytest.mark.parametrize("path", ["per_op", "group"])
+@pytest.mark.parametrize("case", BE.APPLY_CASES, ids=[c.name for c in BE.APPLY_CASES])
+def test_apply_equals_reference(case, path):
+    E, expect, bias = case.inputs()
+    want = bc_edge()["apply"][case.name][1]   # thread-independent but for o == 1 (module docstring)
+    dE, dex, dbias = T(E), T(expect), T(bias)
+    vec = torch.full((case.o * case.bcols,), float("nan"), device=DEV)
+    if path == "per_op":
+        bcols = C.c_int64(0)
+        _lib.check(_lib.load().dfq_bc_apply(_lib.ptr(dE), case.o, case.i2, _lib.ptr(dex), case.f, _lib.ptr(dbias),
+                                            _lib.ptr(vec), C.byref(bcols), _stream()), "dfq_bc_apply")
+        assert bcols.value == case.bcols
+    else:
+        ones, slot = torch.ones(case.f, device=DEV), torch.full((case.f,), float("nan"), device=DEV)
+        _chain([_expect_op(ones, dex, slot, False, False), _apply_op(dE, slot, dbias, vec, case.o, case.i2, case.f)])
+        _same_bits(N(slot), expect, "expectation slot")
+    torch.cuda.synchronize()
+    _same_bits(N(dbias), want, "bias")
+    _same_bits(N(vec).reshape(case.o, case.bcols), E + expect, "bias_vec")   # numpy: one fp32 add per element
+
+
+# ---- PROPAGATE ------------------------------------------------------------
+def _apply_layout(R, F):
+    """[o, i2] of an APPLY whose bias_vec is the case's R * F vector (i2 >= 2: a
+    one-column E is the depthwise broadcast), or None for a single element."""
+    if F >= 2:
+        return R, F
+    if R % 2 == 0:
+        return R // 2, 2
+    return (1, R) if R > 1 else None
+
+
+@pytest.mark.parametrize("path", ["per_op", "group"])
+@pytest.mark.parametrize("case", BE.PROP_CASES, ids=[c.name for c in BE.PROP_CASES])
+def test_propagate_equals_reference(case, path):
+    vec, fb = case.inputs()
+    want = bc_edge()["prop"][case.name]
+    dvec = T(vec)
+    threads = BE.THREADS if case.threaded else BE.THREADS[1:2]   # below 32768 elements the count changes nothing
+    for t in threads:
+        dfb = T(fb)
+        if path == "per_op":
+            _lib.check(_lib.load().dfq_bc_propagate(_lib.ptr(dvec), vec.size, _lib.ptr(dfb), case.F, t, _stream()),
+                       "dfq_bc_propagate")
+        else:
+            prop = (_lib.DFQ_BC_OP_PROPAGATE, t, 0, 0, dfb.data_ptr(), 0, vec.size, 0, case.F)
+            lay = _apply_layout(case.R, case.F)
+            if lay is None:
+                _chain([prop[:2] + (dvec.data_ptr(),) + prop[3:]])
+            else:
+                o, i2 = lay
+                one, zero = torch.ones(1, device=DEV), torch.zeros(1, device=DEV)
+                slot, bias = torch.full((1,), float("nan"), device=DEV), torch.zeros(o, device=DEV)
+                bvec = torch.full((vec.size,), float("nan"), device=DEV)
+                _chain([_expect_op(one, zero, slot, False, False), _apply_op(dvec, slot, bias, bvec, o, i2, 1),
+                        prop[:2] + (bvec.data_ptr(),) + prop[3:]])
+                _same_bits(N(bvec), vec, "bias_vec")
+        torch.cuda.synchronize()
+        _same_bits(N(dfb), want[t], f"fake_bias at {t} threads")
+
+
+# ---- EXPECT ---------------------------------------------------------------
+def _ulps(a, b):
+    """fp32 ulp distance (monotone integer order of the encodings)."""
+    def order(x):
+        i = x.view(np.int32).astype(np.int64)
+        return np.where(i < 0, -(i & 0x7FFFFFFF), i)
+    return np.abs(order(a) - order(b))
+
+
+def _report(got, want, what):
+    d = _ulps(got, want)
+    print(f"{what}: {int((d > 0).sum())} of {d.size} differ, largest {int(d.max())} ulp")
+
+
+@pytest.mark.parametrize("case", BE.EXPECT_CASES, ids=[c[0] for c in BE.EXPECT_CASES])
+def test_expect_per_op_equals_reference(case):
+    """dfq_bc_expect over the 4,097-pair sweep (x = -b/w over [-40, 40], dense through
+    +-1 where ndtr changes branch, negative and tiny w, b == 0)."""
+    out = torch.full((BE.EXPECT_N,), float("nan"), device=DEV)
+    for k, (w, b, relu) in enumerate(BE.expect_terms(case)):
+        dw, db = T(w), T(b)   # named: both alive until the launch has run
+        _lib.check(_lib.load().dfq_bc_expect(_lib.ptr(dw), _lib.ptr(db), BE.EXPECT_N, int(relu), int(k > 0),
+                                             _lib.ptr(out), _stream()), "dfq_bc_expect")
+        torch.cuda.synchronize()
+    want = bc_edge()["expect"][case[0]]
+    _report(N(out), want, f"expect[{case[0]}]")
+    _same_bits(N(out), want, "expectation")
+
+
+@pytest.mark.parametrize("f", [BE.K_BC_STAGE, BE.K_BC_MAX_EXPECT, BE.K_BC_MAX_EXPECT + 1],
+                         ids=["f2048_one_launch", "f4096", "f4097"])
+@pytest.mark.parametrize("case", BE.EXPECT_CASES, ids=[c[0] for c in BE.EXPECT_CASES])
+def test_expect_group_equals_reference(case, f):
+    """The terms accumulated by a group's EXPECT ops (in bc_layer_kernel for f = 2048
+    and at most 8 terms) and the APPLY that reads them: the slot equals the
+    fixture's prefix, the bias the oracle's APPLY on it (which the fixture's APPLY
+    cases pin)."""
+    o = 3
+    E = BE.values(9000 + f, o * f, -33, -27).reshape(o, f)
+    bias0 = BE.values(9001 + f, o, -40, -34)
+    slot = torch.full((f,), float("nan"), device=DEV)
+    dE, dbias, vec = T(E), T(bias0), torch.full((o * f,), float("nan"), device=DEV)
+    keep, rows = [], []
+    for k, (w, b, relu) in enumerate(BE.expect_terms(case)):
+        keep += [T(w[:f]), T(b[:f])]
+        rows.append(_expect_op(keep[-2], keep[-1], slot, relu, k > 0))
+    rows.append(_apply_op(dE, slot, dbias, vec, o, f, f))
+    _chain(rows)
+    want = bc_edge()["expect"][case[0]][:f]
+    _report(N(slot), want, f"expect[{case[0]}][:{f}]")
+    _same_bits(N(slot), want, "expectation slot")
+    wb, wv = O.bc_apply(E, want, bias0)
+    _same_bits(N(dbias), wb, "bias")
+    _same_bits(N(vec), wv, "bias_vec")
+
+
+# ---- COPY -----------------------------------------------------------------
+def test_chain_of_130_copies_with_empty_ones():
+    """130 consecutive COPY ops (kCopyBatch = 64: three launches), every 7th of zero
+    floats and lengths from 1 float to several blocks' worth: every destination
+    equals its source and the guard words between destinations are untouched."""
+    rng = np.random.Generator(np.random.PCG64(77))
+    lens = [0 if k % 7 == 3 else int(rng.integers(1, 3000)) for k in range(130)]
+    lens[64], lens[65], lens[129] = 70001, 0, 1
+    assert lens.count(0) >= 18
+    guard = 5
+    src = torch.from_numpy(BE.values(78, sum(lens), -10, 10)).to(DEV)
+    total = sum(n + guard for n in lens) + guard
+    sentinel = np.float32(-12345.5)
+    dst = torch.full((total,), float(sentinel), device=DEV)
+    rows, s_off, d_off, spans = [], 0, guard, []
+    for n in lens:
+        rows.append((_lib.DFQ_BC_OP_COPY, 0, src.data_ptr() + 4 * s_off, 0, dst.data_ptr() + 4 * d_off, 0, n, 0, 0))
+        spans.append((s_off, d_off, n))
+        s_off += n
+        d_off += n + guard
+    _chain(rows)
+    got, s = N(dst), N(src)
+    untouched = np.ones(total, bool)
+    for s_off, d_off, n in spans:
+        assert np.array_equal(got[d_off:d_off + n].view(np.uint32), s[s_off:s_off + n].view(np.uint32)), (d_off, n)
+        untouched[d_off:d_off + n] = False
+    assert (got[untouched] == sentinel).all() and untouched.sum() == guard * 131
