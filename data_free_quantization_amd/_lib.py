@@ -38,7 +38,7 @@ EXPORTS = [
     "dfq_act_moments", "dfq_act_minmax", "dfq_act_affine",
     "dfq_pair_stats_ws_bytes", "dfq_pair_stats_batch",
     "dfq_clip_search_ws_bytes", "dfq_clip_search_batch",
-    "dfq_mx_quantize_ws_bytes", "dfq_mx_quantize_batch", "dfq_mx_gemm",
+    "dfq_mx_quantize_ws_bytes", "dfq_mx_quantize_batch", "dfq_mx_quantize_search_batch", "dfq_mx_gemm",
 ]
 #: entry points only the diagnostics library exports (include/dfq_diag.h)
 DIAG_EXPORTS = ["dfq_probe_stream", "dfq_probe_lds", "dfq_debug_timeline", "dfq_debug_ablate",
@@ -218,6 +218,7 @@ def load(path: Optional[os.PathLike] = None) -> C.CDLL:
         "dfq_clip_search_batch": ([C.POINTER(ClipSearchDesc), I32, P, I64, P], C.c_int),
         "dfq_mx_quantize_ws_bytes": ([C.POINTER(MxDesc), I32], C.c_int64),
         "dfq_mx_quantize_batch": ([C.POINTER(MxDesc), I32, P, I64, P], C.c_int),
+        "dfq_mx_quantize_search_batch": ([C.POINTER(MxDesc), I32, P, I64, P], C.c_int),
         "dfq_mx_gemm": ([C.POINTER(MxGemmDesc), P], C.c_int),
     }
     diag = {

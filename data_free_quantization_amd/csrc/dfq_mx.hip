@@ -21,6 +21,11 @@
 // Error sums: khw == 1 stores fl32(y - x) as it goes; khw > 1 keeps the task's
 // errors in the wave's LDS copy and one lane adds each khw group in ATen's order
 // (aten_inner_sum, the sweep's helper).  No atomic, nothing handed between waves.
+// dfq_mx_quantize_search_batch is the same walk with one more step after the amax: each lane
+// encodes its four elements under the floor rule's exponent X0 and under X0 + 1, the block's
+// eight lanes add the two candidates' squared errors (mx_noise8: fp32, one instruction
+// sequence for both, the amax's three DPP exchanges) and all take X0 + 1 iff its sum is
+// strictly smaller.  Equal candidates tie and keep X0; nothing else changes.
 #include "dfq_common.h"
 #include "dfq_mx_plan.h"
 
@@ -104,6 +109,24 @@ __device__ __forceinline__ uint32_t max8(uint32_t m) {
     return (uint32_t)x;
 }
 
+// A block's noise under one exponent, the same bits in its eight lanes: the lane's four
+// fl32(y - x) * s (s = 2^-X0: exact, and a 2^-100 block's squares stay normal), squared and added
+// in element order, then added across the lanes by max8's three exchanges.  fp32 add is
+// commutative, so both partners of an exchange hold the same sum.  Explicitly rounded
+// operations: two candidates that are equal element for element give equal sums.
+__device__ __forceinline__ float mx_noise8(const float (&y)[4], const float (&x)[4], float s) {
+    float n = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float t = __fmul_rn(__fsub_rn(y[j], x[j]), s);
+        n = j == 0 ? __fmul_rn(t, t) : __fadd_rn(n, __fmul_rn(t, t));
+    }
+    n = __fadd_rn(n, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(n), 0xB1, 0xF, 0xF, false)));
+    n = __fadd_rn(n, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(n), 0x4E, 0xF, 0xF, false)));
+    n = __fadd_rn(n, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(n), 0x141, 0xF, 0xF, false)));
+    return n;
+}
+
 // the value of the lane's right-hand neighbour in its quad (lane 3: of lane 0)
 __device__ __forceinline__ uint32_t quad_next(uint32_t w) {
     return (uint32_t)__builtin_amdgcn_update_dpp((int)w, (int)w, 0x39, 0xF, 0xF, false);
@@ -111,7 +134,7 @@ __device__ __forceinline__ uint32_t quad_next(uint32_t w) {
 
 // The wave's task.  vtotal padded elements; padded element v lies in row
 // t.row + v / lp at column t.col + v % lp (lp: the padded length of a row, or of the piece).
-template <int FMT, bool VEC>
+template <int FMT, bool VEC, bool SEARCH = false>
 __device__ __forceinline__ void mx_task(const MxJob& J, const MxTask& t, float* edata, int lane) {
     const int64_t row_len = J.row_len;
     const int64_t lpr = J.nb * kMxBlock;   // padded row
@@ -172,12 +195,31 @@ __device__ __forceinline__ void mx_task(const MxJob& J, const MxTask& t, float* 
 #pragma unroll
             for (int j = 1; j < 4; ++j) m = max(m, __float_as_uint(x[b][j]) & 0x7fffffffu);
             m = max8(m);   // every lane takes part
-            const int X = mx_exponent<FMT>(m);
+            int X = mx_exponent<FMT>(m);
             const float inv = pow2f(-X), up = pow2f(X);
             float y[4];
             uint32_t c[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) c[j] = mx_encode<FMT>(x[b][j], inv, up, y[j]);
+            if (SEARCH) {
+                // the block under X + 1 as well, and the two noises N_d = sum ((y_d - x) * 2^-X)^2 (X: the
+                // floor rule's), each by mx_noise8; X + 1 <= 127 - emax + 1 < 127.  An all-zero block
+                // (X = -127) is termwise equal under -126 and keeps X.
+                const float inv1 = pow2f(-(X + 1)), up1 = pow2f(X + 1);
+                float y1[4];
+                uint32_t c1[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) c1[j] = mx_encode<FMT>(x[b][j], inv1, up1, y1[j]);
+                const float n0 = mx_noise8(y, x[b], inv), n1 = mx_noise8(y1, x[b], inv);   // every lane takes part
+                if (n1 < n0) {   // the same two sums in the block's eight lanes: one choice
+                    X += 1;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        y[j] = y1[j];
+                        c[j] = c1[j];
+                    }
+                }
+            }
             // FP6: a lane's codes are the 24 bits w, a quad's 16 elements three dwords
             //   d0 = w0 | w1 << 24,  d1 = w1 >> 8 | w2 << 16,  d2 = w2 >> 16 | w3 << 8
             // lanes 0..2 of the quad build one each from their own w and their neighbour's (every
@@ -322,19 +364,69 @@ __global__ __launch_bounds__(kThreads) void mx6_quantize_kernel(const MxJob* __r
     }
 }
 
+// dfq_mx_quantize_search_batch: the same two walks with the scale search (mx_task<.., true>),
+// in kernels of their own so that the two above keep their instruction streams.
+__global__ __launch_bounds__(kThreads) void mx_search_quantize_kernel(const MxJob* __restrict__ jobs,
+                                                                      const MxTask* __restrict__ tasks, int64_t n_tasks) {
+    extern __shared__ __attribute__((aligned(16))) float mx_lds[];
+    float* const edata = mx_lds + (threadIdx.x >> 6) * DFQ_MX_ESUM_TASK_ELEMS;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t wave = (int64_t)blockIdx.x * kMxWaves + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kMxWaves;
+    for (int64_t ti = wave; ti < n_tasks; ti += n_waves) {
+        const MxTask t = tasks[ti];
+        const MxJob J = jobs[t.job];
+        if (J.format == DFQ_MX_FP4_E2M1) {
+            if (J.vec) mx_task<DFQ_MX_FP4_E2M1, true, true>(J, t, edata, lane);
+            else mx_task<DFQ_MX_FP4_E2M1, false, true>(J, t, edata, lane);
+        } else {
+            if (J.vec) mx_task<DFQ_MX_FP8_E4M3, true, true>(J, t, edata, lane);
+            else mx_task<DFQ_MX_FP8_E4M3, false, true>(J, t, edata, lane);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void mx6_search_quantize_kernel(const MxJob* __restrict__ jobs,
+                                                                       const MxTask* __restrict__ tasks, int64_t n_tasks) {
+    extern __shared__ __attribute__((aligned(16))) float mx_lds[];
+    float* const edata = mx_lds + (threadIdx.x >> 6) * DFQ_MX_ESUM_TASK_ELEMS;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t wave = (int64_t)blockIdx.x * kMxWaves + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * kMxWaves;
+    for (int64_t ti = wave; ti < n_tasks; ti += n_waves) {
+        const MxTask t = tasks[ti];
+        const MxJob J = jobs[t.job];
+        if (J.format == DFQ_MX_FP6_E2M3) {
+            if (J.vec) mx_task<DFQ_MX_FP6_E2M3, true, true>(J, t, edata, lane);
+            else mx_task<DFQ_MX_FP6_E2M3, false, true>(J, t, edata, lane);
+        } else {
+            if (J.vec) mx_task<DFQ_MX_FP6_E3M2, true, true>(J, t, edata, lane);
+            else mx_task<DFQ_MX_FP6_E3M2, false, true>(J, t, edata, lane);
+        }
+    }
+}
+
 }  // namespace
 
 hipError_t preload_mx() {   // see dfq_preload
     hipFuncAttributes a;
-    const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(mx_quantize_kernel));
-    return e != hipSuccess ? e : hipFuncGetAttributes(&a, reinterpret_cast<const void*>(mx6_quantize_kernel));
+    for (const void* k : {reinterpret_cast<const void*>(mx_quantize_kernel), reinterpret_cast<const void*>(mx6_quantize_kernel),
+                          reinterpret_cast<const void*>(mx_search_quantize_kernel),
+                          reinterpret_cast<const void*>(mx6_search_quantize_kernel)}) {
+        const hipError_t e = hipFuncGetAttributes(&a, k);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 }  // namespace dfq
 
 using namespace dfq;
 
-extern "C" int dfq_mx_quantize_batch(const dfq_mx_desc* d, int32_t n, void* ws, int64_t ws_bytes, void* stream) {
+namespace {
+
+// both entry points: `search` picks the kernels, nothing else differs
+int mx_quantize_run(const dfq_mx_desc* d, int32_t n, void* ws, int64_t ws_bytes, void* stream, bool search) {
     if (n < 0 || (n > 0 && !d)) return DFQ_ERR_INVALID;
     if (n == 0) return DFQ_OK;
     MxLayout L;
@@ -373,9 +465,20 @@ extern "C" int dfq_mx_quantize_batch(const dfq_mx_desc* d, int32_t n, void* ws, 
         // one wave per task up to 2^18 tasks: blocks dispatched as others retire balance the uneven tasks
         const int grid = (int)std::min<int64_t>(ceil_div(count, (int64_t)kMxWaves), 1 << 16);
         const size_t lds = lds_of[k] ? sizeof(float) * kMxWaves * DFQ_MX_ESUM_TASK_ELEMS : 0;
-        hipLaunchKernelGGL(k == 0 ? mx_quantize_kernel : mx6_quantize_kernel, dim3(grid), dim3(kThreads), lds, s, dj,
-                           dt + first, count);
+        const auto kernel = search ? (k == 0 ? mx_search_quantize_kernel : mx6_search_quantize_kernel)
+                                   : (k == 0 ? mx_quantize_kernel : mx6_quantize_kernel);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds, s, dj, dt + first, count);
         DFQ_LAUNCH_CHECK();
     }
     return DFQ_OK;
+}
+
+}  // namespace
+
+extern "C" int dfq_mx_quantize_batch(const dfq_mx_desc* d, int32_t n, void* ws, int64_t ws_bytes, void* stream) {
+    return mx_quantize_run(d, n, ws, ws_bytes, stream, false);
+}
+
+extern "C" int dfq_mx_quantize_search_batch(const dfq_mx_desc* d, int32_t n, void* ws, int64_t ws_bytes, void* stream) {
+    return mx_quantize_run(d, n, ws, ws_bytes, stream, true);
 }

@@ -16,7 +16,9 @@ state of ``quantize_targ_layer``) the file holds ``k.codes`` (uint8 [rows, nb, 1
 packed FP4 nibbles, [rows, nb, 24] densely packed FP6 codes or [rows, nb, 32] FP8
 bytes; ``code_storage`` names which), ``k.scales`` (uint8 E8M0 [rows, nb], one per 32 elements of a row) and
 ``k.bias``; the metadata adds ``weight_format`` and ``mx_block``, and ``dequantize``
-dispatches on it (``mx.mx_dequantize``: ``+-q * 2^(scale - 127)``, exact).
+dispatches on it (``mx.mx_dequantize``: ``+-q * 2^(scale - 127)``, exact).  A file written
+after the MX scale search (``mx_scale_search=True``) has the same layout -- the searched
+scales are scale bytes -- and ``"mx_scale_search": true`` in its metadata.
 """
 from __future__ import annotations
 
@@ -29,10 +31,13 @@ from safetensors.torch import load_file, save_file
 
 
 def save(path, graph, state: Dict, *, bits: int, granularity: str, symmetric: bool,
-         clip: Optional[Sequence[float]] = None, packed: bool = False, weight_format: str = "int") -> Dict[str, dict]:
+         clip: Optional[Sequence[float]] = None, packed: bool = False, weight_format: str = "int",
+         mx_scale_search: bool = False) -> Dict[str, dict]:
     from . import mx
     if mx.is_mx(weight_format):
-        return _save_mx(path, graph, state, weight_format, clip)
+        return _save_mx(path, graph, state, weight_format, clip, mx_scale_search)
+    if mx_scale_search:
+        raise ValueError("mx_scale_search needs an MX weight_format, got %r" % (weight_format,))
     tensors, layers = {}, {}
     for key, st in state.items():
         layer = graph[key]
@@ -57,7 +62,7 @@ _MX_STORAGE = {"mxfp4": "fp4_nibbles", "mxfp8": "fp8_e4m3", "mxfp6_e2m3": "fp6_e
                "mxfp6_e3m2": "fp6_e3m2_packed"}
 
 
-def _save_mx(path, graph, state, weight_format, clip):
+def _save_mx(path, graph, state, weight_format, clip, scale_search=False):
     from . import mx
     tensors, layers = {}, {}
     for key, st in state.items():
@@ -73,6 +78,8 @@ def _save_mx(path, graph, state, weight_format, clip):
     meta = {"format": "dfq-mi355x/1", "weight_format": weight_format, "mx_block": mx.BLOCK,
             "bits_per_weight": mx.bits_per_weight(weight_format), "clip": list(clip) if clip is not None else None,
             "code_storage": _MX_STORAGE[weight_format], "layers": layers}
+    if scale_search:   # a note for the reader: the scales are bytes like any others
+        meta["mx_scale_search"] = True
     save_file({n: t.cpu() for n, t in tensors.items()}, str(path), metadata={"dfq": json.dumps(meta)})
     return layers
 

@@ -32,6 +32,13 @@ Same flags and stage order; the transforms run on the GPU.  Additive flags:
                        elements of a row; 4.25 / 6.25 / 6.25 / 8.25 bits per weight), to which
                        those three flags do not apply.  There is no bare mxfp6.  Not with --clip_search, --bc_mode reference,
                        --clip_weight under --bc_mode fused, or --world_size > 1
+  --mx_scale_search    with an MX --weight_format: every 32-element block takes the better of
+                       the OCP floor rule's scale and the next power of two up, by its own
+                       quantization noise (mx.mx_quantize(scale_search=True)): a block whose
+                       largest elements the floor rule would clamp trades them for a coarser
+                       grid where that pays.  --report then counts the raised blocks per layer
+                       (scale_raised); --export marks the file ("mx_scale_search": true), its
+                       format is unchanged.  --mx_matmul re-quantizes such weights with the search
   --mx_matmul {mxfp4,mxfp6_e2m3,mxfp6_e3m2,mxfp8}   run the evaluation's Linear and 1x1-convolution
                        products on the scaled matrix instruction (utils.quantize.mx_matmul_forward,
                        mx.mx_linear): the stored MX weight codes times the layer's input rounded
@@ -110,15 +117,20 @@ def get_argument(argv=None):
     p.add_argument("--mx_matmul", default=None, choices=["mxfp4", "mxfp6_e2m3", "mxfp6_e3m2", "mxfp8"],
                    help="evaluate with the MX layers' products on the scaled matrix instruction, activations "
                         "rounded to this MX format")
+    p.add_argument("--mx_scale_search", action="store_true",
+                   help="MX weights: per block, the better of the floor rule's scale and the next one up by "
+                        "the block's own quantization noise")
     args = p.parse_args(argv)
     if args.mx_matmul is not None and args.weight_format == "int":
         p.error("--mx_matmul needs an MX --weight_format")
+    if args.mx_scale_search and args.weight_format == "int":
+        p.error("--mx_scale_search needs an MX --weight_format")
     if args.weight_format != "int":
         if not args.quantize:
             p.error("--weight_format needs --quantize")
         if args.clip_search:
-            p.error("--weight_format %s conflicts with --clip_search (the search minimizes an integer grid's noise)"
-                    % args.weight_format)
+            p.error("--weight_format %s conflicts with --clip_search (the search minimizes an integer grid's noise; "
+                    "--mx_scale_search is the MX formats' search)" % args.weight_format)
         if args.bc_mode == "reference":
             p.error("--weight_format %s conflicts with --bc_mode reference (its error term is the integer "
                     "quantizer's)" % args.weight_format)
@@ -246,7 +258,7 @@ def main(argv=None):
         cross_layer_equalization(graph, res, targ_layer, Save_state=False, Treshhold=2e-7, launch=True)
     if args.absorption:
         bias_absorption(graph, res, bottoms, N=3, visualize=args.visualize)
-    state = {} if (args.bc_mode == "fused" or args.export) else None
+    state = {} if (args.bc_mode == "fused" or args.export or (args.report and args.mx_scale_search)) else None
     if args.quantize:
         set_layer_bits(graph, args.bits_weight, args.bits_activation, args.bits_bias, targ_layer)
         sharded = args.world_size > 1
@@ -265,7 +277,8 @@ def main(argv=None):
         graph = quantize_targ_layer(graph, args.bits_weight, args.bits_bias, targ_layer,
                                     granularity=args.granularity, symmetric=args.symmetric, clip=fused_clip,
                                     state=state, shard=sharded, weight_ranges=fold_ranges,
-                                    **({"weight_format": args.weight_format} if mx_fmt else {}))
+                                    **({"weight_format": args.weight_format} if mx_fmt else {}),
+                                    **({"mx_scale_search": True} if args.mx_scale_search else {}))
         set_quant_minmax(graph, bottoms)   # main_dfq.py:217
     if args.clip_weight and not (args.quantize and args.bc_mode == "fused"):
         clip_weight(graph, range_clip=[-15, 15], targ_type=targ_layer)
@@ -283,7 +296,8 @@ def main(argv=None):
         clip = [-15, 15] if args.clip_weight else None   # fused in the sweep or clip_weight after it: same clamp
         export.save(args.export, graph, state, bits=args.bits_weight, granularity=args.granularity,
                     symmetric=args.symmetric, clip=clip,
-                    **({"weight_format": args.weight_format} if args.weight_format != "int" else {}))
+                    **({"weight_format": args.weight_format} if args.weight_format != "int" else {}),
+                    **({"mx_scale_search": True} if args.mx_scale_search else {}))
         print(f"Exported {len(state)} quantized layers to {args.export}")
     if args.report and rank == 0:   # sharded runs: every rank holds every result after the gather
         import json
@@ -295,7 +309,9 @@ def main(argv=None):
             **({"clip_search": True, "clip_candidates": args.clip_candidates, "clip_min_frac": args.clip_min_frac}
                if args.clip_search else {}),
             **({"weight_format": args.weight_format, "bits_per_weight": mx.bits_per_weight(args.weight_format)}
-               if args.weight_format != "int" else {})}, clip_search=searched)
+               if args.weight_format != "int" else {}),
+            **({"mx_scale_search": True} if args.mx_scale_search else {})}, clip_search=searched,
+            **({"mx_scales": {k: v["scales"] for k, v in state.items()}} if args.mx_scale_search else {}))
         with open(args.report, "w") as f:
             json.dump(rep, f, indent=1, allow_nan=False)
         m = rep["model"]

@@ -26,6 +26,8 @@ BLOCK = _lib.DFQ_MX_BLOCK
 FORMATS = {"mxfp4": (_lib.DFQ_MX_FP4_E2M1, 4, 16), "mxfp8": (_lib.DFQ_MX_FP8_E4M3, 8, 32),
            "mxfp6_e2m3": (_lib.DFQ_MX_FP6_E2M3, 6, 24), "mxfp6_e3m2": (_lib.DFQ_MX_FP6_E3M2, 6, 24)}
 _NAMES = "'mxfp4', 'mxfp6_e2m3', 'mxfp6_e3m2' or 'mxfp8'"   # there is no bare 'mxfp6': the two differ
+#: the exponent of each element format's largest binade (the floor rule: X = floor(log2 amax) - emax)
+EMAX = {"mxfp4": 2, "mxfp8": 8, "mxfp6_e2m3": 2, "mxfp6_e3m2": 4}
 
 
 def is_mx(weight_format: str) -> bool:
@@ -81,6 +83,22 @@ def allocate(src: torch.Tensor, fmt: str = "mxfp4", khw: int = 1, in_place: bool
         esum=torch.empty(src.numel() // khw, dtype=torch.float32, device=dev) if want_esum else None)
 
 
+def floor_scale_bytes(w: torch.Tensor, fmt: str, rows: Optional[int] = None) -> torch.Tensor:
+    """The scale bytes the floor rule gives fp32 ``w`` viewed as [rows, -1] (rows = shape[0]
+    unless given): uint8 [rows, nb], X + 127 with X = floor(log2 amax) - emax clamped at -127,
+    0 for an all-zero block.  Pure torch, CPU or GPU: what ``scale_raised`` (the quality
+    report's count of blocks the scale search moved) compares the stored bytes with."""
+    if fmt not in FORMATS:
+        raise ValueError("fmt must be %s, got %r" % (_NAMES, fmt))
+    rows = rows if rows is not None else (w.shape[0] if w.dim() > 0 else 1)
+    x = w.detach().reshape(rows, -1).abs()
+    nb = blocks(x.shape[1])
+    x = torch.nn.functional.pad(x, (0, nb * BLOCK - x.shape[1]))
+    amax = x.reshape(rows, nb, BLOCK).amax(dim=-1).contiguous()
+    e = (amax.view(torch.int32) >> 23) & 0xFF   # the fp32 exponent field is floor(log2 amax) + 127
+    return torch.where(amax == 0, torch.zeros_like(e), (e - EMAX[fmt]).clamp(min=0)).to(torch.uint8)
+
+
 _MX = np.dtype([("src", "<u8"), ("dst", "<u8"), ("codes", "<u8"), ("scales", "<u8"), ("esum", "<u8"),
                 ("rows", "<i8"), ("row_len", "<i8"), ("khw", "<i4"), ("format", "<i4"), ("flags", "<i4"),
                 ("reserved", "<i4")])
@@ -88,9 +106,12 @@ assert _MX.itemsize == C.sizeof(_lib.MxDesc)
 assert all(_MX.fields[f][1] == getattr(_lib.MxDesc, f).offset for f, _ in _lib.MxDesc._fields_)
 
 
-def mx_quantize(items: Sequence[MXItem], stream: Optional[torch.cuda.Stream] = None) -> List[MXItem]:
+def mx_quantize(items: Sequence[MXItem], stream: Optional[torch.cuda.Stream] = None,
+                scale_search: bool = False) -> List[MXItem]:
     """Quantize every item in one C call, asynchronous on ``stream`` (the current
-    one by default).  Returns the items."""
+    one by default).  Returns the items.  ``scale_search``: every block takes the
+    better of the floor rule's exponent and the next one up by its own quantization
+    noise (``dfq_mx_quantize_search_batch``) -- same outputs, same layouts."""
     items = list(items)
     if not items:
         return items
@@ -132,8 +153,8 @@ def mx_quantize(items: Sequence[MXItem], stream: Optional[torch.cuda.Stream] = N
         ws = torch.empty(max(int(L.dfq_mx_quantize_ws_bytes(descs, len(items))), 256), dtype=torch.uint8, device=dev)
     if any(it.dst is not None for it in items):
         _lib.weights_changed()
-    _lib.check(L.dfq_mx_quantize_batch(descs, len(items), ws.data_ptr(), ws.numel(), C.c_void_p(s.cuda_stream)),
-               "dfq_mx_quantize_batch", ValueError)
+    name = "dfq_mx_quantize_search_batch" if scale_search else "dfq_mx_quantize_batch"
+    _lib.check(getattr(L, name)(descs, len(items), ws.data_ptr(), ws.numel(), C.c_void_p(s.cuda_stream)), name, ValueError)
     if stream is not None and s != torch.cuda.current_stream(dev):
         for t in keep:
             t.record_stream(s)
@@ -215,12 +236,15 @@ def reset_linear_calls() -> None:
 
 
 def mx_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], weight_format: str,
-              act_format: str = "mxfp8", weight_mx=None) -> torch.Tensor:
+              act_format: str = "mxfp8", weight_mx=None, weight_scale_search: bool = False) -> torch.Tensor:
     """x @ weight.T (+ bias) on the scaled matrix instruction: x (fp32 [M, K], contiguous)
     rounded to ``act_format`` and weight (fp32 [N, K]) to ``weight_format`` by
     ``mx_quantize`` -- blocks of 32 along K for both, codes and scales only -- then one
     ``mx_gemm``.  A weight that already lies on its MX grid (quantize_targ_layer's) re-quantizes
     to its own codes, so the product is of exactly the stored values.
+    ``weight_scale_search``: quantize the weight with ``mx_quantize(scale_search=True)`` -- what a
+    weight that lies on a searched grid needs to come back as its stored values (the floor rule
+    saturates a searched MXFP8 block's 1.875 * 2^k).  The input keeps the floor rule.
     ``weight_mx``: the weight's (codes, scales) from an earlier call, instead of
     quantizing it again.  Returns fp32 [M, N]."""
     global LINEAR_CALLS
@@ -233,7 +257,11 @@ def mx_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor
     xi = allocate(x.detach(), act_format, want_dst=False)
     if weight_mx is None:
         wi = allocate(weight.detach(), weight_format, want_dst=False)
-        mx_quantize([xi, wi])
+        if weight_scale_search:   # two entry points: a call of its own
+            mx_quantize([xi])
+            mx_quantize([wi], scale_search=True)
+        else:
+            mx_quantize([xi, wi])
         weight_mx = (wi.codes, wi.scales)
     else:
         mx_quantize([xi])

@@ -35,7 +35,8 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
             bits_weight: int = 8, bits_activation: int = 8, bits_bias: int = 8, granularity: str = "tensor",
             symmetric: bool = False, bc_mode: str = "literal", clip_range=(-15, 15),
             stage_hook: Optional[Callable[[str], None]] = None, timings: Optional[Dict] = None,
-            report: Optional[dict] = None, clip_search: Optional[dict] = None, weight_format: str = "int"):
+            report: Optional[dict] = None, clip_search: Optional[dict] = None, weight_format: str = "int",
+            mx_scale_search: bool = False):
     """Run the DFQ stages on ``model`` (already on the GPU) in place; returns the
     equalization relations.  ``report``: a dict to fill with the quality report
     (quality.weight_report) of the quantized weights against their values after
@@ -53,9 +54,16 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
     search measures integer grids), with ``bc_mode="reference"`` (its error term is the
     integer quantizer's) and with ``clip`` under ``bc_mode="fused"`` (the MX pass has no
     fused clamp); ``clip`` as its own stage after quantization stays, in the reference's
-    order."""
+    order.
+    ``mx_scale_search``: with an MX ``weight_format`` (ValueError otherwise), every block takes
+    the better of the floor rule's scale and the next one up by its own quantization noise
+    (quantize_targ_layer(mx_scale_search=True)).  The report's config then
+    holds ``mx_scale_search`` and each layer ``scale_raised``, the blocks that took the higher
+    scale.  Off: no new key, no new launch."""
     from .mx import bits_per_weight, is_mx
     mx_fmt = is_mx(weight_format)
+    if mx_scale_search and not mx_fmt:
+        raise ValueError("mx_scale_search needs an MX weight_format, got %r" % (weight_format,))
     if mx_fmt:
         if clip_search is not None:
             raise ValueError("weight_format=%r conflicts with clip_search: the search minimizes an integer "
@@ -93,6 +101,9 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
     if absorption:
         stage("absorb", bias_absorption, graph, res, bottoms, N=3)
     state = {} if (correction and bc_mode == "fused") else None
+    qstate = state
+    if mx_scale_search and report is not None and qstate is None:
+        qstate = {}   # the report counts the raised scales: keep the scale bytes
     snap = searched = None
     cs_cfg = {}
     if clip_search is not None and not quantize:
@@ -113,8 +124,9 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
                              symmetric=symmetric, candidates=cs_cfg["clip_candidates"],
                              min_frac=cs_cfg["clip_min_frac"], targ_type=targ, weight_ranges=fold_ranges)
         stage("quant", quantize_targ_layer, graph, bits_weight, bits_bias, targ, granularity=granularity,
-              symmetric=symmetric, clip=fused_clip, state=state, weight_ranges=fold_ranges,
-              **({"weight_format": weight_format} if mx_fmt else {}))
+              symmetric=symmetric, clip=fused_clip, state=qstate, weight_ranges=fold_ranges,
+              **({"weight_format": weight_format} if mx_fmt else {}),
+              **({"mx_scale_search": True} if mx_scale_search else {}))
     if clip and not (quantize and bc_mode == "fused"):
         stage("clip", clip_weight, graph, range_clip=list(clip_range), targ_type=targ)
     if snap is not None:   # the weights are final from here (bias correction rewrites biases only)
@@ -122,8 +134,10 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
             "bits_weight": bits_weight, "granularity": granularity, "symmetric": bool(symmetric),
             "equalize": bool(equalize), "absorption": bool(absorption), "clip": bool(clip),
             "clip_range": [float(c) for c in clip_range], "bc_mode": bc_mode, **cs_cfg,
-            **({"weight_format": weight_format, "bits_per_weight": bits_per_weight(weight_format)} if mx_fmt else {})},
-            clip_search=searched))
+            **({"weight_format": weight_format, "bits_per_weight": bits_per_weight(weight_format)} if mx_fmt else {}),
+            **({"mx_scale_search": True} if mx_scale_search else {})},
+            clip_search=searched,
+            **({"mx_scales": {k: v["scales"] for k, v in qstate.items()}} if mx_scale_search else {})))
     if correction:
         err = None
         if bc_mode == "fused":

@@ -178,7 +178,8 @@ def build_report(entries, config: dict) -> dict:
     return {"format": FORMAT, "config": dict(config), "layers": layers, "model": model_entry(layers)}
 
 
-def weight_report(graph, snap: Dict, *, config: dict, clip_search: Optional[Dict] = None) -> dict:
+def weight_report(graph, snap: Dict, *, config: dict, clip_search: Optional[Dict] = None,
+                  mx_scales: Optional[Dict] = None) -> dict:
     """The report of ``graph``'s target weights against ``snap`` (``snapshot``'s
     clones, taken before the quantization): one pair_stats call over
     (snap[k], graph[k].weight) in graph order, one device-to-host copy.
@@ -188,7 +189,12 @@ def weight_report(graph, snap: Dict, *, config: dict, clip_search: Optional[Dict
     its units (``clip_units``: channels, or 1 for the tensor), those that chose a
     narrower range than min-max (``clip_narrowed``) and those that chose the narrowest candidate
     (``clip_at_edge``: many of them say min_frac should be lower); the caller
-    records the search's settings in ``config``."""
+    records the search's settings in ``config``.
+
+    ``mx_scales``: {key: stored scale bytes [rows, nb]} of a quantization with the MX scale
+    search (``config["weight_format"]`` names the format).  Each of those layers then also
+    gets ``scale_raised``: the blocks whose stored byte is above the floor rule's, which is
+    computed here from ``snap`` (mx.floor_scale_bytes)."""
     keys = [k for k in graph if k in snap]
     call = PairStatsCall([(snap[k], graph[k].weight.detach()) for k in keys])
     call.run()
@@ -215,4 +221,13 @@ def weight_report(graph, snap: Dict, *, config: dict, clip_search: Optional[Dict
             e["clip_units"] = int(c.size)
             e["clip_narrowed"] = int((c > 0).sum())
             e["clip_at_edge"] = int(((c > 0) & (c == last)).sum())
+    if mx_scales is not None:
+        from .mx import floor_scale_bytes
+        found = [k for k in keys if k in mx_scales]
+        raised = torch.stack([(mx_scales[k] > floor_scale_bytes(snap[k], config["weight_format"])).sum()
+                              for k in found]).cpu().tolist() if found else []
+        by_key = dict(zip(found, raised))
+        for e, k in zip(rep["layers"], keys):
+            if k in by_key:
+                e["scale_raised"] = int(by_key[k])
     return rep

@@ -206,7 +206,8 @@ def _identity_forward(bn):
 
 def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, *, granularity="tensor",
                         symmetric=False, clip=None, state: Optional[Dict] = None, shard: bool = False,
-                        group=None, weight_ranges: Optional[Dict] = None, weight_format: str = "int"):
+                        group=None, weight_ranges: Optional[Dict] = None, weight_format: str = "int",
+                        mx_scale_search: bool = False):
     """Fake-quantize every target layer's weight (and bias when bits_bias < 32) in
     place, all layers in one grouped launch.
 
@@ -235,11 +236,20 @@ def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, *, gr
     ``clip``, ``shard=True`` and ``weight_ranges`` raise ValueError.  Biases take the
     integer sweep at ``bits_bias`` as always.  ``state[k]`` holds ``codes``, ``scales``,
     ``esum``, ``khw`` and ``format``; each layer is marked (``layer.weight_format``) so
-    that the Quant* layers' forward uses the stored weight as it is."""
+    that the Quant* layers' forward uses the stored weight as it is.
+
+    ``mx_scale_search=True`` (an MX ``weight_format`` only, else ValueError): every block
+    takes the better of the floor rule's scale and the next one up by its own noise
+    (``mx.mx_quantize(scale_search=True)``).  The layers are also marked
+    ``layer.mx_scale_search`` -- ``mx_matmul_forward`` must re-quantize such a weight with the
+    search to get its stored values back -- and ``state[k]["scale_search"]``
+    is True; with the option off there is neither mark nor key."""
     from ..mx import is_mx
     if is_mx(weight_format):
         return _quantize_targ_layer_mx(graph, bits_bias, targ_type, weight_format, clip=clip, state=state,
-                                       shard=shard, weight_ranges=weight_ranges)
+                                       shard=shard, weight_ranges=weight_ranges, scale_search=bool(mx_scale_search))
+    if mx_scale_search:
+        raise ValueError("mx_scale_search needs an MX weight_format, got %r" % (weight_format,))
     _lib.weights_changed()
     if shard and torch.distributed.is_initialized():
         return _quantize_targ_layer_sharded(graph, bit_weight, bits_bias, targ_type, granularity=granularity,
@@ -257,7 +267,8 @@ def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, *, gr
     for layer_idx, layer in graph.items():
         if type(layer) not in tt:
             continue
-        layer.__dict__.pop("weight_format", None)   # an earlier MX pass's mark
+        layer.__dict__.pop("weight_format", None)   # an earlier MX pass's marks
+        layer.__dict__.pop("mx_scale_search", None)
         lp = layer._parameters   # no Module.__getattr__ per access
         w = lp["weight"]   # written in place by the kernel: no .data view needed
         rows = w.size(0) if per_channel else 1
@@ -301,7 +312,8 @@ def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, *, gr
     return graph
 
 
-def _quantize_targ_layer_mx(graph, bits_bias, targ_type, weight_format, *, clip, state, shard, weight_ranges):
+def _quantize_targ_layer_mx(graph, bits_bias, targ_type, weight_format, *, clip, state, shard, weight_ranges,
+                            scale_search=False):
     """quantize_targ_layer with an MX weight format (see there)."""
     from .. import mx
     if clip is not None:
@@ -349,17 +361,22 @@ def _quantize_targ_layer_mx(graph, bits_bias, targ_type, weight_format, *, clip,
         f32 = torch.empty(fo, dtype=torch.float32, device=dev)
         for it, (c0, s0, f0, r, nb, ne) in zip(items, spans):   # raw addresses: the views are made below
             it.codes, it.scales, it.esum = codes.data_ptr() + c0, scales.data_ptr() + s0, f32.data_ptr() + 4 * f0
-    mx.mx_quantize(items)
+    mx.mx_quantize(items, scale_search=scale_search)
     if biases:
         plan = SweepPlan(biases)
         plan.execute()
         plan.destroy()
     for layer in layers:   # the Quant* layers' forward takes a marked layer's weight as stored
         layer.__dict__["weight_format"] = weight_format
+        if scale_search:
+            layer.__dict__["mx_scale_search"] = True
+        else:
+            layer.__dict__.pop("mx_scale_search", None)
     if state is not None:
         for k, it, (c0, s0, f0, r, nb, ne) in zip(keys, items, spans):
             state[k] = dict(codes=codes[c0:c0 + r * nb * cbytes].view(r, nb, cbytes), scales=scales[s0:s0 + r * nb].view(r, nb),
-                            esum=f32[f0:f0 + ne], khw=it.khw, format=weight_format)
+                            esum=f32[f0:f0 + ne], khw=it.khw, format=weight_format,
+                            **({"scale_search": True} if scale_search else {}))
     return graph
 
 
@@ -429,7 +446,8 @@ def _quantize_targ_layer_sharded(graph, bit_weight, bits_bias, targ_type, *, gra
         layer = graph[layer_idx]
         if type(layer) not in targ_type:
             continue
-        layer.__dict__.pop("weight_format", None)   # an earlier MX pass's mark
+        layer.__dict__.pop("weight_format", None)   # an earlier MX pass's marks
+        layer.__dict__.pop("mx_scale_search", None)
         lp = layer._parameters
         w = lp["weight"].data
         _lib.require_device(w)

@@ -374,7 +374,9 @@ def mx_matmul_forward(act_format: str = "mxfp8"):
     QConv2d with a 1x1 kernel, groups == 1 and zero padding (a stride slices the input).
     The activation and bias fake quant stay; every other layer, and everything outside the
     scope, is untouched.  The scope resets ``mx.LINEAR_CALLS``.  Inside ``frozen_weights()``
-    a layer's weight codes are kept under the weight cache's key."""
+    a layer's weight codes are kept under the weight cache's key.  A layer marked
+    ``mx_scale_search`` (quantize_targ_layer's) has its weight re-quantized with the scale
+    search: the floor rule does not give a searched MXFP8 weight back."""
     from .. import mx
     if act_format not in mx.FORMATS:
         raise ValueError("act_format must be an MX format name, got %r" % (act_format,))
@@ -415,13 +417,14 @@ class _QuantWeightMixin:
             raise RuntimeError("mx_matmul_forward is an inference path: run it under torch.no_grad()")
         w2d = qweight.reshape(qweight.shape[0], -1)
         key = self._weight_key(weight, bias)
+        search = bool(self.__dict__.get("mx_scale_search", False))
         if key is None:
             self.__dict__.pop("_mx_w_cache", None)
-            return mx.mx_linear(x2d, w2d, qbias, fmt, _MX_MATMUL)
+            return mx.mx_linear(x2d, w2d, qbias, fmt, _MX_MATMUL, weight_scale_search=search)
         hit = self.__dict__.get("_mx_w_cache")
-        if hit is None or hit[0] != (key, fmt):
-            wi = mx.mx_quantize([mx.allocate(w2d.detach().contiguous(), fmt, want_dst=False)])[0]
-            hit = self.__dict__["_mx_w_cache"] = ((key, fmt), wi.codes, wi.scales)
+        if hit is None or hit[0] != (key, fmt, search):
+            wi = mx.mx_quantize([mx.allocate(w2d.detach().contiguous(), fmt, want_dst=False)], scale_search=search)[0]
+            hit = self.__dict__["_mx_w_cache"] = ((key, fmt, search), wi.codes, wi.scales)
         return mx.mx_linear(x2d, w2d, qbias, fmt, _MX_MATMUL, weight_mx=(hit[1], hit[2]))
 
     def _mx_conv1x1(self, input, weight, bias, qweight, qbias, fmt):

@@ -489,6 +489,25 @@ int64_t dfq_mx_quantize_ws_bytes(const dfq_mx_desc* descs, int32_t n);
  * 4-B aligned, row_len % 4 == 0) take 16-B loads; the others a 4-B path with the
  * same results.  Each tensor at most once per call.  n == 0: DFQ_OK, nothing launched. */
 int dfq_mx_quantize_batch(const dfq_mx_desc* descs, int32_t n, void* ws, int64_t ws_bytes, void* stream);
+/* dfq_mx_quantize_batch with a noise-minimizing choice of the block's exponent: the same
+ * descriptors (flags stays 0), workspace (dfq_mx_quantize_ws_bytes), error codes, launches and
+ * mixed-list rule; every line of the contract above holds except the one for X.
+ * For a block with amax != 0 let X0 be the floor rule's exponent above, X1 = X0 + 1
+ * (X0 <= 127 - emax, so the scale byte stays below 0xFF), y0 / y1 the block's y under
+ * X0 / X1 and
+ *   N_d = sum_i (fl32(y_i^d - x_i) * 2^-X0)^2      (the factor is exact in fp32)
+ * The block takes X1 iff N_1 < N_0, strictly, else X0; the chosen X defines codes, scales,
+ * dst and esum.  A block with amax == 0 keeps X = -127 (scale byte 0, +0 / -0 codes).
+ * X1 lifts the clamp of a block whose amax * 2^-X0 lies above the format's maximum at the
+ * price of a grid twice as coarse; no other exponent is tried.
+ * The sums are formed in fp32: four rounded squares per lane in element order, then three
+ * pairwise exchanges across the block's eight lanes -- within 33 * 2^-24 relative of the
+ * real sums, so the choice is the real-number one wherever N_0 and N_1 differ by more than
+ * 2^-18 of the larger.  Both sums run through one instruction sequence: a block whose y0 and
+ * y1 are equal element for element (zeros, a single power-of-two element) ties and keeps
+ * X0.  A tensor's result is the same bits from run to run, alone or anywhere in a list,
+ * with dst aliasing src or not, and on the 16-B and the 4-B path. */
+int dfq_mx_quantize_search_batch(const dfq_mx_desc* descs, int32_t n, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---- MX matrix multiply on the scaled matrix instruction (no reference counterpart) ----
  * out[m][n] = sum_k A[m][k] * B[n][k] (+ bias[n]), A and B given as MX codes and scale

@@ -20,6 +20,11 @@ microseconds.  The JSON line goes to stdout and to --out.
   python scripts/mx_quantize_time.py --ab OTHER.so   # MXFP4 / MXFP8 call times of another build of the
                                                  #   library (the parent commit's) against this tree's, alternated
                                                  #   three times in this process -> profiles/r10/mx6_parent_ab.jsonl
+  python scripts/mx_quantize_time.py --search    # dfq_mx_quantize_search_batch against the floor call, per format,
+                                                 #   alternated three times -> profiles/r12/mx_search_time.jsonl
+  python scripts/mx_quantize_time.py --search_quality   # MobileNetV2 model SQNR per format with and without
+                                                 #   --mx_scale_search, and the logits SQNR of the forward on the matrix
+                                                 #   instruction with searched MXFP8 weights -> profiles/r12/quality_mx_search.jsonl
 """
 import argparse
 import ctypes as C
@@ -36,6 +41,7 @@ import bench  # noqa: E402
 from data_free_quantization_amd import _lib, distributed as D, mx  # noqa: E402
 
 OUT = Path(__file__).resolve().parent.parent / "profiles" / "r10"
+OUT_SEARCH = Path(__file__).resolve().parent.parent / "profiles" / "r12"
 
 
 def emit(records, path):
@@ -88,10 +94,12 @@ class MxCall:
         assert self._ws.numel() >= nb_ws
         self.ws_bytes = nb_ws
 
-    def run(self, stream, lib=None):
-        """The call, through this process's library or another build of it (same buffers)."""
-        _lib.check((lib or self._lib).dfq_mx_quantize_batch(self._descs, self._n, self._ws.data_ptr(), self._ws.numel(),
-                                                     C.c_void_p(stream.cuda_stream)), "dfq_mx_quantize_batch")
+    def run(self, stream, lib=None, search=False):
+        """The call, through this process's library or another build of it (same buffers);
+        ``search``: dfq_mx_quantize_search_batch on the same table."""
+        name = "dfq_mx_quantize_search_batch" if search else "dfq_mx_quantize_batch"
+        _lib.check(getattr(lib or self._lib, name)(self._descs, self._n, self._ws.data_ptr(), self._ws.numel(),
+                                                   C.c_void_p(stream.cuda_stream)), name)
 
 
 def bench_list(args):
@@ -154,8 +162,11 @@ def parent_ab(args):
     formats the other build lacks are not timed."""
     dev, b, shapes, per_copy, copies, symmetric, items = bench_list(args)
     stream = torch.cuda.current_stream(dev)
-    other = _lib.load(args.ab)
-    assert other is not _lib.load()   # (its kernel's code object loads in the first leg's warm-up)
+    # the one entry it is timed through, typed here: another commit's build need not export
+    # everything this tree's binding asks for (its kernel's code object loads in the first leg's warm-up)
+    other = C.CDLL(str(Path(args.ab).resolve()))
+    mine = _lib.load().dfq_mx_quantize_batch
+    other.dfq_mx_quantize_batch.argtypes, other.dfq_mx_quantize_batch.restype = mine.argtypes, mine.restype
     fmts = ("mxfp4", "mxfp8")
     calls = {fmt: MxCall(items, fmt) for fmt in fmts}
     libs = {"parent": other, "new": _lib.load()}
@@ -178,6 +189,112 @@ def parent_ab(args):
                     "new_within_parent_spread": all(t <= max(old) for t in new)}
     torch.cuda.synchronize()
     emit([out], Path(args.out) if args.out else OUT / "mx6_parent_ab.jsonl")
+
+
+def search_timing(args):
+    """dfq_mx_quantize_search_batch against dfq_mx_quantize_batch on the bench list: the same
+    descriptor table, outputs and workspace, the two calls alternated three times per format
+    in one process.  The source is restored before every leg from a copy (dst is the source:
+    a second call over searched values would time other data)."""
+    dev, b, shapes, per_copy, copies, symmetric, items = bench_list(args)
+    stream = torch.cuda.current_stream(dev)
+    calls = {"mxfp8": MxCall(items, "mxfp8")}
+    calls.update({fmt: MxCall(items, fmt, share=calls["mxfp8"]) for fmt in mx.FORMATS if fmt != "mxfp8"})
+    aliased = all(it.dst.data_ptr() == it.src.data_ptr() for it in items)
+    keep = [it.src.clone() for it in items] if aliased else None
+
+    def restore():
+        if keep is not None:
+            torch._foreach_copy_([it.src for it in items], keep)
+
+    legs = []
+    for _ in range(3):
+        leg = {}
+        for fmt in mx.FORMATS:
+            for who, search in (("floor", False), ("search", True)):
+                restore()
+                leg["%s_%s_ms" % (who, fmt)] = round(timed(lambda: calls[fmt].run(stream, search=search), stream,
+                                                           args.warmup, args.steps), 4)
+        legs.append(leg)
+    out = {"what": "dfq_mx_quantize_search_batch against dfq_mx_quantize_batch (dst + codes + scales + esum) on the bench "
+                   "headline list, alternated in one process",
+           "device": torch.cuda.get_device_name(dev), "model": b.model, "copies": copies, "tensors": len(items),
+           "elements": per_copy * copies, "dst_aliases_src": aliased, "warmup": args.warmup, "steps": args.steps,
+           "legs": legs}
+    frac = lambda nbytes, ms: round(nbytes / ms / 1e6 / bench.HBM_PEAK_GBS, 4)   # noqa: E731
+    for fmt in mx.FORMATS:
+        f = statistics.median(leg["floor_%s_ms" % fmt] for leg in legs)
+        t = statistics.median(leg["search_%s_ms" % fmt] for leg in legs)
+        out[fmt] = {"floor_ms": f, "search_ms": t, "ratio": round(t / f, 3), "algo_bytes": calls[fmt].algo_bytes,
+                    "floor_frac_of_peak": frac(calls[fmt].algo_bytes, f), "search_frac_of_peak": frac(calls[fmt].algo_bytes, t)}
+    torch.cuda.synchronize()
+    emit([out], Path(args.out) if args.out else OUT_SEARCH / "mx_search_time.jsonl")
+
+
+def matmul_logits_record(fmt, search):
+    """Logits SQNR of the zoo's MobileNetV2 (seed 0, batch 2 at 32 x 32, fixed observers) with its
+    eligible products on the matrix instruction (MXFP8 activations) against its plain forward."""
+    import torch.nn as nn
+    from data_free_quantization_amd import pipeline, zoo
+    from data_free_quantization_amd.utils import layer_transform as L
+    from data_free_quantization_amd.utils.quantize import QuantConv2d, QuantLinear, frozen_weights, mx_matmul_forward
+    from data_free_quantization_amd.utils.tracer import TorchTransformer
+    torch.manual_seed(0)
+    model = zoo.build("mobilenetv2", seed=0, relu=True).cuda().eval()
+    x = torch.randn(2, 3, 32, 32, device="cuda")
+    tr = TorchTransformer("positional")
+    model, tr = L.switch_layers(model, tr, x, {1: [(nn.Conv2d, QuantConv2d), (nn.Linear, QuantLinear)]})
+    graph, bottoms = tr.log.getGraph(), tr.log.getBottoms()
+    try:
+        pipeline.run_dfq(model, graph, bottoms, (QuantConv2d, QuantLinear), weight_format=fmt, bc_mode="fused", clip=False,
+                         **({"mx_scale_search": True} if search else {}))
+        L.set_quant_minmax(graph, bottoms, verbose=False)
+        model.eval()
+        for m in graph.values():
+            if hasattr(m, "quant"):
+                m.quant.update_stat = False
+        for q in L.module_tensor_op.quants:
+            q.update_stat = False
+        L.replace_op()
+        try:
+            with torch.no_grad(), frozen_weights():
+                plain = model(x)
+                with mx_matmul_forward("mxfp8"):
+                    routed = model(x)
+                    calls = mx.LINEAR_CALLS
+        finally:
+            L.restore_op()
+    finally:
+        L.module_tensor_op = None
+    noise = float((routed.double() - plain.double()).pow(2).sum())
+    return {"what": "logits of --mx_matmul mxfp8 against the plain forward", "weight_format": fmt, "mx_scale_search": search,
+            "layers_routed": calls, "logits_sqnr_db": round(10 * np.log10(float(plain.double().pow(2).sum()) / noise), 3)}
+
+
+def search_quality_records(args):
+    """Model SQNR of the zoo's MobileNetV2 (seed 0) from main_dfq --relu --equalize --absorption
+    --quantize --weight_format F --report, with and without --mx_scale_search, and the blocks
+    the search raised; then matmul_logits_record for MXFP8 weights.  Data, not assertions."""
+    import tempfile
+    from data_free_quantization_amd import main_dfq
+    records = []
+    with tempfile.TemporaryDirectory() as tmp:
+        for fmt in ("mxfp4", "mxfp6_e3m2", "mxfp6_e2m3", "mxfp8"):
+            for search in (False, True):
+                path = Path(tmp) / "report.json"
+                argv = ["--relu", "--equalize", "--absorption", "--quantize", "--weight_format", fmt] + \
+                    (["--mx_scale_search"] if search else []) + ["--report", str(path)]
+                main_dfq.main(argv)
+                rep = json.loads(path.read_text())
+                m = rep["model"]
+                records.append({"argv": " ".join(argv[:-2]), "weight_format": fmt, "mx_scale_search": search,
+                                "model_sqnr_db": round(m["sqnr_db"], 3), "worst_layer": m["worst_layer"],
+                                "worst_channel_sqnr_db": round(min(e["worst_channel_sqnr_db"] for e in rep["layers"]), 3),
+                                **({"scale_raised": sum(e["scale_raised"] for e in rep["layers"]),
+                                    "blocks": sum(e["shape"][0] * -(-(e["elements"] // e["shape"][0]) // 32)
+                                                  for e in rep["layers"])} if search else {})})
+    records += [matmul_logits_record("mxfp8", False), matmul_logits_record("mxfp8", True)]
+    emit(records, Path(args.out) if args.out else OUT_SEARCH / "quality_mx_search.jsonl")
 
 
 def quality_records(args):
@@ -213,6 +330,11 @@ if __name__ == "__main__":
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--quality", action="store_true")
     ap.add_argument("--ab", default=None, help="another build of libdfq_hip.so to time MXFP4 / MXFP8 against")
-    ap.add_argument("--out", default=None, help="the JSON lines' file (default: under profiles/r10)")
+    ap.add_argument("--search", action="store_true", help="time the searched call against the floor call")
+    ap.add_argument("--search_quality", action="store_true", help="model SQNR with and without --mx_scale_search")
+    ap.add_argument("--out", default=None, help="the JSON lines' file (default: under profiles/r10 or r12)")
     a = ap.parse_args()
-    quality_records(a) if a.quality else parent_ab(a) if a.ab else timing(a)
+    if a.search or a.search_quality:
+        search_quality_records(a) if a.search_quality else search_timing(a)
+    else:
+        quality_records(a) if a.quality else parent_ab(a) if a.ab else timing(a)
