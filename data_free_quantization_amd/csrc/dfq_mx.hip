@@ -27,6 +27,7 @@
 // sequence for both, the amax's three DPP exchanges) and all take X0 + 1 iff its sum is
 // strictly smaller.  Equal candidates tie and keep X0; nothing else changes.
 #include "dfq_common.h"
+#include "dfq_mx_encode.h"
 #include "dfq_mx_plan.h"
 
 #include <algorithm>
@@ -39,66 +40,6 @@ namespace {
 constexpr int kMxWaves = kThreads / kWave;
 constexpr int kMxBatch = 4;   // rounds whose loads are issued together (dst may alias src: the
                               // compiler cannot move a round's loads above the previous round's stores)
-
-template <int FMT>
-struct MxFmt;
-template <>
-struct MxFmt<DFQ_MX_FP4_E2M1> {
-    static constexpr int mbits = 1, emin = 0, emax = 2, max_code = 0x7, sign = 0x8;
-    static constexpr float qmax = 6.0f;   // the magnitude of max_code
-};
-template <>
-struct MxFmt<DFQ_MX_FP8_E4M3> {
-    static constexpr int mbits = 3, emin = -6, emax = 8, max_code = 0x7E, sign = 0x80;   // 0x7F is NaN
-    static constexpr float qmax = 448.0f;
-};
-template <>
-struct MxFmt<DFQ_MX_FP6_E2M3> {   // s ee mmm, bias 1: every code is finite
-    static constexpr int mbits = 3, emin = 0, emax = 2, max_code = 0x1F, sign = 0x20;
-    static constexpr float qmax = 7.5f;
-};
-template <>
-struct MxFmt<DFQ_MX_FP6_E3M2> {   // s eee mm, bias 3: every code is finite
-    static constexpr int mbits = 2, emin = -2, emax = 4, max_code = 0x1F, sign = 0x20;
-    static constexpr float qmax = 28.0f;
-};
-template <int FMT>
-constexpr bool kMxFp6 = FMT == DFQ_MX_FP6_E2M3 || FMT == DFQ_MX_FP6_E3M2;
-
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }   // -127 <= e <= 127; -127: +0
-
-// The shared exponent X of a block whose largest magnitude has the bits `amax_bits`.
-template <int FMT>
-__device__ __forceinline__ int mx_exponent(uint32_t amax_bits) {
-    if (amax_bits == 0) return -127;
-    const int x = (int)(amax_bits >> 23) - 127 - MxFmt<FMT>::emax;   // floor(log2 amax) is the fp32 exponent
-    return x < -127 ? -127 : x;                                      // <= 127 - emax
-}
-
-// One element: its code and y = +-q * 2^X.  inv = 2^-X, up = 2^X.
-//   v = |x| * 2^-X in [0, 2^(emax+1));  e = max(exponent(v), emin);  n = rne(v * 2^(mbits-e)), an
-//   integer in [0, 2^(mbits+1)];  magnitude code = n + ((e - emin) << mbits): n < 2^mbits only in the
-//   subnormal binade (exponent field 0), n == 2^(mbits+1) carries into the next binade's first code,
-//   and an even n is an even code, so round-half-even on n is ties-to-even-code.  The codes ascend
-//   with the magnitudes, so the integer min with the largest finite code saturates.
-template <int FMT>
-__device__ __forceinline__ uint32_t mx_encode(float x, float inv, float up, float& y) {
-    using F = MxFmt<FMT>;
-    const uint32_t xb = __float_as_uint(x);
-    const float v = __uint_as_float(xb & 0x7fffffffu) * inv;
-    int e = (int)(__float_as_uint(v) >> 23) - 127;
-    e = e < F::emin ? F::emin : e;
-    const float n = rintf(v * pow2f(F::mbits - e));
-    uint32_t code = (uint32_t)(int)n + ((uint32_t)(e - F::emin) << F::mbits);
-    float q = n * pow2f(e - F::mbits);
-    if (code > (uint32_t)F::max_code) {
-        code = F::max_code;
-        q = F::qmax;
-    }
-    const uint32_t sb = xb & 0x80000000u;
-    y = __uint_as_float(__float_as_uint(q * up) | sb);
-    return code | (sb ? (uint32_t)F::sign : 0u);
-}
 
 // max over aligned groups of 8 lanes (quad swaps, then the half-row mirror)
 __device__ __forceinline__ uint32_t max8(uint32_t m) {

@@ -45,6 +45,10 @@ Same flags and stage order; the transforms run on the GPU.  Additive flags:
                        to this MX format in blocks of 32 along the channel dimension -- a second
                        rounding of the activations, after their integer fake quant.  Needs an MX
                        --weight_format
+  --mx_matmul_fused    with --mx_matmul: round each layer's input inside the multiply's kernel
+                       (mx.mx_linear_fused, dfq_mx_linear) instead of in a quantizer launch of its
+                       own -- the same bits, one library launch per layer once its weight codes
+                       are cached.  Needs --mx_matmul
 
 Example (README.md:137 of the reference):
   python -m data_free_quantization_amd.main_dfq --task cls --relu --equalize --absorption \
@@ -117,12 +121,16 @@ def get_argument(argv=None):
     p.add_argument("--mx_matmul", default=None, choices=["mxfp4", "mxfp6_e2m3", "mxfp6_e3m2", "mxfp8"],
                    help="evaluate with the MX layers' products on the scaled matrix instruction, activations "
                         "rounded to this MX format")
+    p.add_argument("--mx_matmul_fused", action="store_true",
+                   help="with --mx_matmul: quantize each layer's input inside the multiply's kernel (one launch per layer)")
     p.add_argument("--mx_scale_search", action="store_true",
                    help="MX weights: per block, the better of the floor rule's scale and the next one up by "
                         "the block's own quantization noise")
     args = p.parse_args(argv)
     if args.mx_matmul is not None and args.weight_format == "int":
         p.error("--mx_matmul needs an MX --weight_format")
+    if args.mx_matmul_fused and args.mx_matmul is None:
+        p.error("--mx_matmul_fused needs --mx_matmul")
     if args.mx_scale_search and args.weight_format == "int":
         p.error("--mx_scale_search needs an MX --weight_format")
     if args.weight_format != "int":
@@ -332,7 +340,8 @@ def main(argv=None):
         # bias fake-quant between batches (utils.quantize.frozen_weights)
         import contextlib
         from .utils.quantize import frozen_weights, mx_matmul_forward
-        scope = mx_matmul_forward(args.mx_matmul) if args.mx_matmul is not None else contextlib.nullcontext()
+        scope = (mx_matmul_forward(args.mx_matmul, fused=args.mx_matmul_fused) if args.mx_matmul is not None
+                 else contextlib.nullcontext())
         with frozen_weights(), scope:
             accuracy = inference_all(model, args.task, args)
         print(f"Inference time is {time.time() - start} seconds")

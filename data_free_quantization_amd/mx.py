@@ -8,7 +8,9 @@ launch, one HBM pass, asynchronous on the stream); ``mx_dequantize`` rebuilds th
 fp32 values from codes and scales in plain torch, exactly, on CPU or GPU.
 ``mx_gemm`` multiplies two operands given as codes and scales on the scaled matrix
 instruction (``dfq_mx_gemm``), ``mx_linear`` quantizes an fp32 input and
-weight and multiplies them.  There is no CPU fallback for the quantizer or the
+weight and multiplies them, and ``mx_linear_fused`` multiplies an fp32 input with stored
+weight codes in one launch, quantizing the input inside the kernel (``dfq_mx_linear``).
+There is no CPU fallback for the quantizer or the
 multiply: CPU tensors raise."""
 from __future__ import annotations
 
@@ -226,6 +228,65 @@ def mx_gemm(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: 
     return out
 
 
+def mx_linear_fused(x: torch.Tensor, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str, K: int,
+                    act_format: str = "mxfp8", bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                    stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """out[m, n] = sum_k Q(x)[m, k] * B[n, k] (+ bias[n]) in one launch (dfq_mx_linear; DESIGN.md
+    3.8): ``x`` fp32 [M, K] rounded to ``act_format`` inside the kernel -- blocks of 32 along K,
+    the floor rule, no scale search -- times B given as ``mx_gemm``'s B.  Bit for bit
+    ``mx_quantize`` of x followed by ``mx_gemm``; the input's codes never reach memory.
+    ``x`` needs unit column stride; any row stride >= K is passed on (a column slice of a wider
+    tensor is read in place, no copy).  ``out`` as for ``mx_gemm``."""
+    K = int(K)
+    if K < 1:
+        raise ValueError("K must be >= 1")
+    if act_format not in FORMATS:
+        raise ValueError("act_format must be %s, got %r" % (_NAMES, act_format))
+    if b_fmt not in FORMATS:
+        raise ValueError("b_fmt must be %s, got %r" % (_NAMES, b_fmt))
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x: a float32 tensor on the GPU")
+    if not x.is_cuda:
+        raise RuntimeError("data_free_quantization_amd multiplies MX codes on a ROCm GPU only; "
+                           "x is on %s (there is no CPU fallback)" % (x.device,))
+    if x.dtype != torch.float32:
+        raise TypeError("x: float32 on the GPU")
+    N = _codes_arg("b", b_codes, b_scales, b_fmt, K)
+    if x.dim() != 2 or x.shape[1] != K or x.shape[0] < 1 or x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < K):
+        raise ValueError("x must be [M, %d] with unit column stride and a row stride >= %d, got %s with strides %s"
+                         % (K, K, tuple(x.shape), tuple(x.stride())))
+    M = x.shape[0]
+    dev = x.device
+    if bias is not None:
+        _lib.require_device(bias)
+        if bias.numel() != N:
+            raise ValueError("bias holds %d elements, %d needed" % (bias.numel(), N))
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=dev)
+    else:
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32:
+            raise TypeError("out: float32 on the GPU")
+        if out.dim() != 2 or tuple(out.shape) != (M, N) or out.stride(1) != 1 or (M > 1 and out.stride(0) < N):
+            raise ValueError("out must be [%d, %d] with unit column stride and a row stride >= %d" % (M, N, N))
+    for t in (b_codes, b_scales, bias, out):
+        if t is not None and t.device != dev:
+            raise ValueError("every tensor of an mx_linear_fused call must live on one device")
+    d = _lib.MxLinearDesc()
+    d.x, d.b_codes, d.b_scales = x.data_ptr(), b_codes.data_ptr(), b_scales.data_ptr()
+    d.bias = bias.data_ptr() if bias is not None else None
+    d.out = out.data_ptr()
+    d.ldx = x.stride(0) if M > 1 else max(x.stride(0), K)
+    d.ldo = out.stride(0) if M > 1 else max(out.stride(0), N)
+    d.M, d.N, d.K, d.x_format, d.b_format = M, N, K, FORMATS[act_format][0], FORMATS[b_fmt][0]
+    s = C.c_void_p(stream.cuda_stream) if stream is not None else _lib.raw_stream(dev)
+    _lib.check(_lib.load().dfq_mx_linear(C.byref(d), s), "dfq_mx_linear", ValueError)
+    if stream is not None and stream != torch.cuda.current_stream(dev):
+        for t in (x, b_codes, b_scales, bias, out):
+            if t is not None:
+                t.record_stream(stream)
+    return out
+
+
 #: mx_linear calls since the last reset (utils.quantize.mx_matmul_forward resets it on entry)
 LINEAR_CALLS = 0
 
@@ -236,7 +297,7 @@ def reset_linear_calls() -> None:
 
 
 def mx_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], weight_format: str,
-              act_format: str = "mxfp8", weight_mx=None, weight_scale_search: bool = False) -> torch.Tensor:
+              act_format: str = "mxfp8", weight_mx=None, weight_scale_search: bool = False, fused: bool = False) -> torch.Tensor:
     """x @ weight.T (+ bias) on the scaled matrix instruction: x (fp32 [M, K], contiguous)
     rounded to ``act_format`` and weight (fp32 [N, K]) to ``weight_format`` by
     ``mx_quantize`` -- blocks of 32 along K for both, codes and scales only -- then one
@@ -246,7 +307,9 @@ def mx_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor
     weight that lies on a searched grid needs to come back as its stored values (the floor rule
     saturates a searched MXFP8 block's 1.875 * 2^k).  The input keeps the floor rule.
     ``weight_mx``: the weight's (codes, scales) from an earlier call, instead of
-    quantizing it again.  Returns fp32 [M, N]."""
+    quantizing it again.  ``fused``: the input is quantized inside the multiply's kernel
+    (``mx_linear_fused``: one launch once the weight's codes exist, the same bits); the weight,
+    when ``weight_mx`` is None, still goes through ``mx_quantize``.  Returns fp32 [M, N]."""
     global LINEAR_CALLS
     for fmt in (weight_format, act_format):
         if fmt not in FORMATS:
@@ -254,6 +317,12 @@ def mx_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor
     _lib.require_device(x, weight, bias)
     if x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1] or x.shape[0] < 1 or x.shape[1] < 1:
         raise ValueError("x must be [M, K] and weight [N, K], got %s and %s" % (tuple(x.shape), tuple(weight.shape)))
+    if fused:
+        if weight_mx is None:
+            wi = mx_quantize([allocate(weight.detach(), weight_format, want_dst=False)], scale_search=weight_scale_search)[0]
+            weight_mx = (wi.codes, wi.scales)
+        LINEAR_CALLS += 1
+        return mx_linear_fused(x.detach(), weight_mx[0], weight_mx[1], weight_format, x.shape[1], act_format, bias=bias)
     xi = allocate(x.detach(), act_format, want_dst=False)
     if weight_mx is None:
         wi = allocate(weight.detach(), weight_format, want_dst=False)

@@ -362,10 +362,11 @@ def frozen_weights():
 
 
 _MX_MATMUL = None   # the activation format of the open mx_matmul_forward() scope
+_MX_FUSED = False    # that scope multiplies through mx.mx_linear(fused=True)
 
 
 @contextlib.contextmanager
-def mx_matmul_forward(act_format: str = "mxfp8"):
+def mx_matmul_forward(act_format: str = "mxfp8", fused: bool = False):
     """Inference with the MX layers' products on the scaled matrix instruction: inside
     this scope a Quant* layer whose ``weight_format`` mark (quantize_targ_layer's) is an MX
     format multiplies through ``mx.mx_linear`` -- its weight's MX codes times its input
@@ -376,17 +377,21 @@ def mx_matmul_forward(act_format: str = "mxfp8"):
     scope, is untouched.  The scope resets ``mx.LINEAR_CALLS``.  Inside ``frozen_weights()``
     a layer's weight codes are kept under the weight cache's key.  A layer marked
     ``mx_scale_search`` (quantize_targ_layer's) has its weight re-quantized with the scale
-    search: the floor rule does not give a searched MXFP8 weight back."""
+    search: the floor rule does not give a searched MXFP8 weight back.
+    ``fused``: the eligible layers multiply through ``mx.mx_linear(fused=True)`` -- the input is
+    rounded inside the multiply's kernel (``dfq_mx_linear``), the same bits; inside
+    ``frozen_weights()`` such a layer costs one library launch and no ``mx_quantize`` call after
+    its first forward."""
     from .. import mx
     if act_format not in mx.FORMATS:
         raise ValueError("act_format must be an MX format name, got %r" % (act_format,))
-    global _MX_MATMUL
-    prev, _MX_MATMUL = _MX_MATMUL, act_format
+    global _MX_MATMUL, _MX_FUSED
+    prev, _MX_MATMUL, _MX_FUSED = (_MX_MATMUL, _MX_FUSED), act_format, bool(fused)
     mx.reset_linear_calls()
     try:
         yield
     finally:
-        _MX_MATMUL = prev
+        _MX_MATMUL, _MX_FUSED = prev
 
 
 class _QuantWeightMixin:
@@ -420,12 +425,12 @@ class _QuantWeightMixin:
         search = bool(self.__dict__.get("mx_scale_search", False))
         if key is None:
             self.__dict__.pop("_mx_w_cache", None)
-            return mx.mx_linear(x2d, w2d, qbias, fmt, _MX_MATMUL, weight_scale_search=search)
+            return mx.mx_linear(x2d, w2d, qbias, fmt, _MX_MATMUL, weight_scale_search=search, fused=_MX_FUSED)
         hit = self.__dict__.get("_mx_w_cache")
         if hit is None or hit[0] != (key, fmt, search):
             wi = mx.mx_quantize([mx.allocate(w2d.detach().contiguous(), fmt, want_dst=False)], scale_search=search)[0]
             hit = self.__dict__["_mx_w_cache"] = ((key, fmt, search), wi.codes, wi.scales)
-        return mx.mx_linear(x2d, w2d, qbias, fmt, _MX_MATMUL, weight_mx=(hit[1], hit[2]))
+        return mx.mx_linear(x2d, w2d, qbias, fmt, _MX_MATMUL, weight_mx=(hit[1], hit[2]), fused=_MX_FUSED)
 
     def _mx_conv1x1(self, input, weight, bias, qweight, qbias, fmt):
         x = input[:, :, ::self.stride[0], ::self.stride[1]]

@@ -555,6 +555,49 @@ typedef struct dfq_mx_gemm_desc {
 } dfq_mx_gemm_desc;
 int dfq_mx_gemm(const dfq_mx_gemm_desc* d, void* stream);
 
+/* ---- MX linear in one launch: dfq_mx_gemm with the activation quantized in the kernel ----
+ * out[m][n] = sum_k Q(x)[m][k] * B[n][k] (+ bias[n]).  B is given as dfq_mx_gemm's B (MX
+ * codes and scale bytes); x is fp32 and Q is the MX contract above applied to every row of
+ * x in x_format: blocks of 32 along K, a partial last block padded with +0, the floor rule
+ * X = floor(log2 amax) - emax, round to nearest with ties to the even code, saturation at
+ * the format's maximum, scale byte 0 for an all-zero block.  There is no scale search for
+ * the activation.  Each lane of the kernel reads the fp32 elements its operand of the matrix
+ * instruction stands for, takes the block's amax and encodes straight into the operand
+ * registers (an FP8 lane holds halves of two blocks: one amax exchange with the lane 16
+ * away and one gather of the scale byte); Q(x)'s codes never reach memory.
+ * The result is bit for bit what dfq_mx_quantize_batch (codes and scales of x) followed by
+ * dfq_mx_gemm gives, on all 16 (x_format, b_format) pairs: the same operand registers, one
+ * accumulator per output element, the K steps in order, no split of K, no atomics, no
+ * workspace, the bias one fp32 add at the end.  So dfq_mx_gemm's numerics and
+ * reproducibility statements hold here too.  Domain, the union of the two contracts: finite
+ * x whose non-zero magnitudes are >= 2^-100, and |X_a + X_b| <= 100 for blocks that meet.
+ * Elements of x at k >= K and rows >= M are never read.  Rows of x that start 16-B aligned
+ * and hold whole groups of four (x 16-B aligned, ldx % 4 == 0, K % 4 == 0) take 16-B loads;
+ * every other case (K = 30, a column slice that starts at element 3 of a wider tensor) 4-B
+ * loads with the same results.
+ * Asynchronous on `stream`, no host wait.  Checked on the host before any device call:
+ * DFQ_ERR_INVALID for a NULL x, b_codes, b_scales or out, an unknown format, M, N or K < 1
+ * (or beyond dfq_mx_gemm's limits; M * ldx beyond 2^50), non-zero flags or reserved, x, out or
+ * bias not 4-B aligned, b_codes not 16-B (FP6: 8-B) aligned; DFQ_ERR_SHAPE for ldx < K or
+ * ldo < N. */
+typedef struct dfq_mx_linear_desc {
+    const float* x;         /* fp32 [M, K], K-contiguous, row stride ldx elements; 4-B aligned */
+    const void*  b_codes;   /* uint8 [N, nb, cb(b_format)], as dfq_mx_gemm's B */
+    const void*  b_scales;  /* uint8 [N, nb] */
+    const float* bias;      /* [N] or NULL */
+    float*       out;       /* [M, N] fp32, row stride ldo */
+    int64_t      ldx;       /* >= K */
+    int64_t      ldo;       /* >= N */
+    int64_t      M;
+    int64_t      N;
+    int64_t      K;         /* nb = ceil(K / 32) */
+    int32_t      x_format;  /* the MX format x is rounded to (DFQ_MX_*) */
+    int32_t      b_format;
+    int32_t      flags;     /* 0 */
+    int32_t      reserved;  /* 0 */
+} dfq_mx_linear_desc;
+int dfq_mx_linear(const dfq_mx_linear_desc* d, void* stream);
+
 /* ---- high-bias absorption (bias_absorption.py:147-197) ------------------
  * c = max(bn_b - N*bn_w, 0) (bn_* = the BN's fake_weight / fake_bias);
  * b2[o] += sum_i (sum_k W2[o,i,k]) * c[g*i2 + i];  b1 -= c;  bn_b -= c.
