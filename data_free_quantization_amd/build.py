@@ -21,7 +21,7 @@ LIB = PKG / "libdfq_hip.so"
 # the MX matrix multiply's and the fused MX linear's planners, which also build on their own for their sanitizer tests).
 SOURCES = ["dfq_lib.hip", "dfq_sweep.hip", "dfq_sweep_plan.cpp", "dfq_transform.hip", "dfq_cle.hip", "dfq_cle_relation.hip",
            "dfq_cle_plan.cpp", "dfq_stats.hip", "dfq_stats_plan.cpp", "dfq_clip.hip", "dfq_clip_plan.cpp", "dfq_mx.hip", "dfq_mx_plan.cpp",
-           "dfq_mx_gemm.hip", "dfq_mx_gemm_plan.cpp", "dfq_mx_linear.hip", "dfq_mx_linear_plan.cpp"]
+           "dfq_mx_gemm.hip", "dfq_mx_gemm_plan.cpp", "dfq_mx_linear_plan.cpp"]
 # Diagnostics build (bench.py's ceiling probes, scripts/ A/B runs): the same
 # sources with -DDFQ_DIAGNOSTICS (the sweep's A/B variants and environment
 # switches) plus the probes (include/dfq_diag.h).  Never loaded by the product path.
@@ -61,12 +61,8 @@ def _stale(out: Path, deps) -> bool:
 
 
 def _build_one(out: Path, sources, defines, force: bool, verbose: bool) -> Path:
-    deps = [CSRC / s for s in sources] + [CSRC / "dfq_common.h", CSRC / "dfq_cle_common.h", CSRC / "dfq_cle_plan.h",
-                                          CSRC / "dfq_sweep_plan.h", CSRC / "dfq_stats_plan.h", CSRC / "dfq_clip_plan.h", CSRC / "dfq_mx_plan.h",
-                                          CSRC / "dfq_mx_gemm_plan.h", CSRC / "dfq_mx_gemm_frag.h", CSRC / "dfq_mx_encode.h",
-                                          CSRC / "dfq_mx_linear_plan.h",
-                                          ROOT / "include" / "dfq_hip.h", ROOT / "include" / "dfq_diag.h", EXPORTS,
-                                          Path(__file__)]
+    deps = [CSRC / s for s in sources] + sorted(CSRC.glob("*.h")) + [ROOT / "include" / "dfq_hip.h", ROOT / "include" / "dfq_diag.h",
+                                                                     EXPORTS, Path(__file__)]
     if not force and not _stale(out, deps):
         return out
     tag = out.stem

@@ -259,14 +259,15 @@ __device__ __forceinline__ void mx_task(const MxJob& J, const MxTask& t, float* 
 
 // LDS (dynamic): DFQ_MX_ESUM_TASK_ELEMS floats per wave when some tensor's error sums
 // need them, none otherwise; written and read by its own wave only.
-// FP4 and FP8 tasks run in mx_quantize_kernel, FP6 tasks in mx6_quantize_kernel: four
-// mx_task instantiations each (all eight in one kernel take 167 VGPRs and spill SGPRs;
-// apart, 133 as before the FP6 formats and 149, no scratch, 3 waves per SIMD).  The
-// host hands each kernel its own tasks (dfq_mx_quantize_batch).  The two bodies are
-// written out: through one shared template the compiler schedules mx_quantize_kernel
-// differently, and it is kept instruction for instruction what it was without FP6.
-__global__ __launch_bounds__(kThreads) void mx_quantize_kernel(const MxJob* __restrict__ jobs,
-                                                               const MxTask* __restrict__ tasks, int64_t n_tasks) {
+// One kernel walks the tasks of two formats, F0 and F1, with or without the scale search
+// (dfq_mx_quantize_search_batch): four mx_task variants each.  There are four instantiations
+// and not one kernel because all eight floor-rule variants in one kernel take 167 VGPRs and
+// spill SGPRs; apart they take 133 (FP4 / FP8) and 149 (FP6), searched 142 and 160, no
+// scratch.  The host hands each instantiation its own tasks (mx_quantize_run).  The
+// template compiles to the same instructions as four bodies written out.
+template <int F0, int F1, bool SEARCH>
+__global__ __launch_bounds__(kThreads) void mx_quantize_kernel_t(const MxJob* __restrict__ jobs,
+                                                                 const MxTask* __restrict__ tasks, int64_t n_tasks) {
     extern __shared__ __attribute__((aligned(16))) float mx_lds[];
     float* const edata = mx_lds + (threadIdx.x >> 6) * DFQ_MX_ESUM_TASK_ELEMS;
     const int lane = threadIdx.x & (kWave - 1);
@@ -275,77 +276,19 @@ __global__ __launch_bounds__(kThreads) void mx_quantize_kernel(const MxJob* __re
     for (int64_t ti = wave; ti < n_tasks; ti += n_waves) {
         const MxTask t = tasks[ti];
         const MxJob J = jobs[t.job];
-        if (J.format == DFQ_MX_FP4_E2M1) {
-            if (J.vec) mx_task<DFQ_MX_FP4_E2M1, true>(J, t, edata, lane);
-            else mx_task<DFQ_MX_FP4_E2M1, false>(J, t, edata, lane);
+        if (J.format == F0) {
+            if (J.vec) mx_task<F0, true, SEARCH>(J, t, edata, lane);
+            else mx_task<F0, false, SEARCH>(J, t, edata, lane);
         } else {
-            if (J.vec) mx_task<DFQ_MX_FP8_E4M3, true>(J, t, edata, lane);
-            else mx_task<DFQ_MX_FP8_E4M3, false>(J, t, edata, lane);
+            if (J.vec) mx_task<F1, true, SEARCH>(J, t, edata, lane);
+            else mx_task<F1, false, SEARCH>(J, t, edata, lane);
         }
     }
 }
-
-__global__ __launch_bounds__(kThreads) void mx6_quantize_kernel(const MxJob* __restrict__ jobs,
-                                                                const MxTask* __restrict__ tasks, int64_t n_tasks) {
-    extern __shared__ __attribute__((aligned(16))) float mx_lds[];
-    float* const edata = mx_lds + (threadIdx.x >> 6) * DFQ_MX_ESUM_TASK_ELEMS;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t wave = (int64_t)blockIdx.x * kMxWaves + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kMxWaves;
-    for (int64_t ti = wave; ti < n_tasks; ti += n_waves) {
-        const MxTask t = tasks[ti];
-        const MxJob J = jobs[t.job];
-        if (J.format == DFQ_MX_FP6_E2M3) {
-            if (J.vec) mx_task<DFQ_MX_FP6_E2M3, true>(J, t, edata, lane);
-            else mx_task<DFQ_MX_FP6_E2M3, false>(J, t, edata, lane);
-        } else {
-            if (J.vec) mx_task<DFQ_MX_FP6_E3M2, true>(J, t, edata, lane);
-            else mx_task<DFQ_MX_FP6_E3M2, false>(J, t, edata, lane);
-        }
-    }
-}
-
-// dfq_mx_quantize_search_batch: the same two walks with the scale search (mx_task<.., true>),
-// in kernels of their own so that the two above keep their instruction streams.
-__global__ __launch_bounds__(kThreads) void mx_search_quantize_kernel(const MxJob* __restrict__ jobs,
-                                                                      const MxTask* __restrict__ tasks, int64_t n_tasks) {
-    extern __shared__ __attribute__((aligned(16))) float mx_lds[];
-    float* const edata = mx_lds + (threadIdx.x >> 6) * DFQ_MX_ESUM_TASK_ELEMS;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t wave = (int64_t)blockIdx.x * kMxWaves + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kMxWaves;
-    for (int64_t ti = wave; ti < n_tasks; ti += n_waves) {
-        const MxTask t = tasks[ti];
-        const MxJob J = jobs[t.job];
-        if (J.format == DFQ_MX_FP4_E2M1) {
-            if (J.vec) mx_task<DFQ_MX_FP4_E2M1, true, true>(J, t, edata, lane);
-            else mx_task<DFQ_MX_FP4_E2M1, false, true>(J, t, edata, lane);
-        } else {
-            if (J.vec) mx_task<DFQ_MX_FP8_E4M3, true, true>(J, t, edata, lane);
-            else mx_task<DFQ_MX_FP8_E4M3, false, true>(J, t, edata, lane);
-        }
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void mx6_search_quantize_kernel(const MxJob* __restrict__ jobs,
-                                                                       const MxTask* __restrict__ tasks, int64_t n_tasks) {
-    extern __shared__ __attribute__((aligned(16))) float mx_lds[];
-    float* const edata = mx_lds + (threadIdx.x >> 6) * DFQ_MX_ESUM_TASK_ELEMS;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t wave = (int64_t)blockIdx.x * kMxWaves + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * kMxWaves;
-    for (int64_t ti = wave; ti < n_tasks; ti += n_waves) {
-        const MxTask t = tasks[ti];
-        const MxJob J = jobs[t.job];
-        if (J.format == DFQ_MX_FP6_E2M3) {
-            if (J.vec) mx_task<DFQ_MX_FP6_E2M3, true, true>(J, t, edata, lane);
-            else mx_task<DFQ_MX_FP6_E2M3, false, true>(J, t, edata, lane);
-        } else {
-            if (J.vec) mx_task<DFQ_MX_FP6_E3M2, true, true>(J, t, edata, lane);
-            else mx_task<DFQ_MX_FP6_E3M2, false, true>(J, t, edata, lane);
-        }
-    }
-}
+constexpr auto mx_quantize_kernel = mx_quantize_kernel_t<DFQ_MX_FP4_E2M1, DFQ_MX_FP8_E4M3, false>;
+constexpr auto mx6_quantize_kernel = mx_quantize_kernel_t<DFQ_MX_FP6_E2M3, DFQ_MX_FP6_E3M2, false>;
+constexpr auto mx_search_quantize_kernel = mx_quantize_kernel_t<DFQ_MX_FP4_E2M1, DFQ_MX_FP8_E4M3, true>;
+constexpr auto mx6_search_quantize_kernel = mx_quantize_kernel_t<DFQ_MX_FP6_E2M3, DFQ_MX_FP6_E3M2, true>;
 
 }  // namespace
 

@@ -1,5 +1,5 @@
 // The MX element encoder (include/dfq_hip.h's contract), shared by the quantizer
-// (dfq_mx.hip) and the fused linear (dfq_mx_linear.hip): the element formats' constants,
+// (dfq_mx.hip) and the fused linear (dfq_mx_gemm.hip): the element formats' constants,
 // the floor rule's exponent and one element's code.  Plain integer / fp32 arithmetic with
 // no HIP-only intrinsic, so a host program compiles it too
 // (tests/native/mx_linear_plan_check.cpp encodes the case files with it): exact

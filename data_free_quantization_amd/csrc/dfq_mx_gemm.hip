@@ -1,6 +1,9 @@
-// dfq_mx_gemm: out[m][n] = sum_k A[m][k] * B[n][k] (+ bias[n]) on the scaled matrix
-// instruction v_mfma_scale_f32_16x16x128_f8f6f4, both operands read as the MX codes and
-// E8M0 scale bytes dfq_mx_quantize_batch writes (include/dfq_hip.h).
+// dfq_mx_gemm and dfq_mx_linear: out[m][n] = sum_k A[m][k] * B[n][k] (+ bias[n]) on the scaled
+// matrix instruction v_mfma_scale_f32_16x16x128_f8f6f4 (include/dfq_hip.h).  One
+// kernel template over where the A operand comes from: dfq_mx_gemm reads both operands as the
+// MX codes and E8M0 scale bytes dfq_mx_quantize_batch writes ("stored" A); dfq_mx_linear builds
+// A in the kernel from the fp32 activation x ("fp32" A, A = Q(x)) and is otherwise the same
+// multiply in one launch.
 //
 // For FP4 and FP6 a lane's operand of the instruction is 32 consecutive K elements of one
 // row and one scale byte: exactly one stored MX block, codes[row][blk][0 .. cb) and
@@ -15,45 +18,223 @@
 // integer data on the 16 format pairs).
 // All addressing is dfq_mx_gemm_plan.h's: a wave owns a 32 x 32 output tile, so each of
 // its two A and two B fragments per K step (128 elements) feeds two instructions; four
-// waves make a 64 x 64 block tile.  The next step's fragments are loaded before this
-// step's four instructions issue.  Lanes of rows past M / N and of MX blocks past nb issue
+// waves make a 64 x 64 block tile.  Lanes of rows past M / N and of MX blocks past nb issue
 // no load and hold zero codes with scale byte 127; such rows are not stored.  No LDS, no
 // workspace, no atomics, no split of K: an output element is one accumulator of one lane,
 // added up in K-step order, then one fp32 add of the bias.
-#include "dfq_mx_gemm_frag.h"
+//
+// fp32 A: a lane reads the fp32 elements its operand stands for -- one MX block of one row for
+// FP4 / FP6, two 16-element halves of two blocks for FP8 -- as 16-B loads where the rows of x
+// start 16-B aligned and K % 4 == 0 (a kernel instantiation of its own) and as 4-B loads
+// otherwise, takes the amax of the magnitudes' bit patterns, derives the floor rule's exponent
+// and encodes (dfq_mx_encode.h, the quantizer's own encoder) straight into the operand
+// registers in the stored blocks' bit order (dfq_mx_linear_plan.h).  An FP8 lane exchanges its
+// two halves' amax with lane ^ 16 and gathers its lane group's block's scale byte from the lane
+// group that knows it: three ds_bpermute per fragment, no LDS memory, no barrier.  Every lane
+// of a working wave takes part in the exchanges: the only early return is wave-uniform and
+// lies before the loop.  Elements at k >= K and rows >= M are never read and count as +0.  So
+// the operand registers are bit for bit the ones a stored A holds after
+// dfq_mx_quantize_batch of x, and so is the result.  The A fragment is re-quantized by every
+// wave that needs it (once per 32 output columns): the kernel is aimed at layer-sized calls.
+//
+// A K step, for either A: turn what was fetched for step s into A's operand registers (a
+// copy for a stored A, the quantizer for an fp32 A), issue the loads of step s + 1 -- A's
+// codes or fp32 elements, and B's fragments -- then the step's four instructions.
+#include "dfq_common.h"
+#include "dfq_mx_linear_plan.h"
 
 namespace dfq {
 namespace {
 
-struct MxgArgs {
-    const uint8_t* a_codes;
-    const uint8_t* a_scales;
+typedef int mxg_v8i __attribute__((ext_vector_type(8)));
+typedef int mxg_v4i __attribute__((ext_vector_type(4)));
+typedef int mxg_v2i __attribute__((ext_vector_type(2)));
+typedef float mxg_v4f __attribute__((ext_vector_type(4)));
+
+// One MX block's code bytes as the operand registers (the registers past the format's
+// size stay zero and are not read by the instruction).
+template <int CB>
+__device__ __forceinline__ mxg_v8i mxg_load_codes(const DFQ_GLOBAL uint8_t* p, bool on) {
+    mxg_v8i v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (on) {
+        if (CB == 24) {   // 8-B aligned
+            const mxg_v2i q0 = *(const DFQ_GLOBAL mxg_v2i*)p, q1 = *(const DFQ_GLOBAL mxg_v2i*)(p + 8),
+                          q2 = *(const DFQ_GLOBAL mxg_v2i*)(p + 16);
+            v[0] = q0.x; v[1] = q0.y; v[2] = q1.x; v[3] = q1.y; v[4] = q2.x; v[5] = q2.y;
+        } else {
+            const mxg_v4i q0 = *(const DFQ_GLOBAL mxg_v4i*)p;
+            v[0] = q0.x; v[1] = q0.y; v[2] = q0.z; v[3] = q0.w;
+            if (CB == 32) {
+                const mxg_v4i q1 = *(const DFQ_GLOBAL mxg_v4i*)(p + 16);
+                v[4] = q1.x; v[5] = q1.y; v[6] = q1.z; v[7] = q1.w;
+            }
+        }
+    }
+    return v;
+}
+
+// One operand's fragment of a lane: F its format field.  FP6 / FP4: the lane's MX block as
+// stored.  FP8: the 16-byte halves of two MX blocks the instruction expects in the lane
+// (dfq_mx_gemm_plan.h, "split").  The scale byte is the lane group's block's either way.
+template <int F>
+__device__ __forceinline__ void mxg_load_operand(mxg_v8i& v, int& s, const uint8_t* codes_, const uint8_t* scales_,
+                                                 int64_t row, int64_t rows, int64_t nb, int64_t step, int lane) {
+    const DFQ_GLOBAL uint8_t* codes = (const DFQ_GLOBAL uint8_t*)codes_;
+    const DFQ_GLOBAL uint8_t* scales = (const DFQ_GLOBAL uint8_t*)scales_;
+    const int64_t kb = mxg_lane_kblock(step, lane);
+    const bool on = mxg_lane_loads(row, rows, kb, nb);
+    s = on ? (int)scales[mxg_scale_offset(row, kb, nb)] : 127;
+    if (!mxg_hw_split(F)) {
+        constexpr int cb = mxg_hw_code_bytes(F);
+        v = mxg_load_codes<cb>(codes + mxg_code_offset(row, kb, nb, cb), on);
+    } else {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int64_t kh = mxg_split_kblock(step, lane, h);
+            const mxg_v8i q = mxg_load_codes<kMxgHalfBytes>(codes + mxg_split_code_offset(row, kh, nb, lane),
+                                                            mxg_lane_loads(row, rows, kh, nb));
+            v[4 * h] = q[0]; v[4 * h + 1] = q[1]; v[4 * h + 2] = q[2]; v[4 * h + 3] = q[3];
+        }
+    }
+}
+
+// A wave's 2 x 2 accumulator tiles to out (+ bias[n], one fp32 add), rows past M and columns
+// past N not stored.
+__device__ __forceinline__ void mxg_store_tile(const mxg_v4f (&acc)[kMxgSub][kMxgSub], float* out_, const float* bias_,
+                                               int64_t ldo, int64_t M, int64_t N, int64_t m0, int64_t n0, int lane) {
+    DFQ_GLOBAL float* out = (DFQ_GLOBAL float*)out_;
+    const DFQ_GLOBAL float* bias = (const DFQ_GLOBAL float*)bias_;
+#pragma unroll
+    for (int j = 0; j < kMxgSub; ++j) {
+        const int64_t col = mxg_out_col(n0, j, lane);
+        const float bv = bias != nullptr && col < N ? bias[col] : 0.f;
+#pragma unroll
+        for (int i = 0; i < kMxgSub; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t row = mxg_out_row(m0, i, lane, r);
+                if (!mxg_stores(row, col, M, N)) continue;
+                const float v = acc[i][j][r];
+                out[mxg_out_offset(row, col, ldo)] = bias != nullptr ? v + bv : v;
+            }
+    }
+}
+
+// a_scales comes last so that an fp32 A's fields lie where dfq_mx_linear's kernel always had them.
+struct MxmArgs {
+    const void* a;             // stored A: its codes; fp32 A: x
     const uint8_t* b_codes;
     const uint8_t* b_scales;
     const float* bias;
     float* out;
-    int64_t ldo, M, N, nb;
+    int64_t lda;               // fp32 A only: x's row stride in elements
+    int64_t ldo, M, N, K, nb;
+    const uint8_t* a_scales;   // stored A only
 };
 
-// A wave's operands of one K step: fragment i of each operand is instruction tile i's;
-// s is the lane group's MX block's scale byte in bits [0, 8) (opsel 0).
-struct MxgFrags {
-    mxg_v8i a[kMxgSub], b[kMxgSub];
-    int sa[kMxgSub], sb[kMxgSub];
+__device__ __forceinline__ uint32_t mxl_from_lane(int src_lane, uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_ds_bpermute(4 * src_lane, (int)v);
+}
+
+// Where A comes from.  Fetched: what a lane holds of A's instruction tile row `row` between the
+// loads of a K step and the top of that step; fetch() issues those loads, operand() turns them
+// into the instruction's registers and scale byte (bits [0, 8), opsel 0).  F: the instruction's
+// format field (cbsz).  kAfterB: a step's loads of A are issued after both of B's fragments'
+// instead of fragment by fragment before B's -- the order each source measured faster with
+// (DESIGN.md 3.8).
+template <int FA>
+struct MxmStoredA {
+    static constexpr int F = FA;
+    static constexpr bool kAfterB = true;
+    struct Fetched {
+        mxg_v8i a;
+        int sa;
+    };
+    static __device__ __forceinline__ void fetch(Fetched& f, const MxmArgs& g, int64_t row, int64_t step, int lane) {
+        mxg_load_operand<FA>(f.a, f.sa, static_cast<const uint8_t*>(g.a), g.a_scales, row, g.M, g.nb, step, lane);
+    }
+    static __device__ __forceinline__ void operand(mxg_v8i& a, int& s, const Fetched& f, const MxmArgs&, int64_t, int64_t, int) {
+        a = f.a;
+        s = f.sa;
+    }
 };
 
-template <int FA, int FB>
-__device__ __forceinline__ void mxg_load(MxgFrags& f, const MxgArgs& g, int64_t m0, int64_t n0, int64_t step, int lane) {
+// VEC: x on the 16-B path (mxl_vec).
+template <int FA, bool VEC>
+struct MxmFp32A {
+    static constexpr int F = FA;
+    static constexpr bool kAfterB = false;
+    typedef float Fetched[DFQ_MX_BLOCK];   // the lane's 32 fp32 elements, in slot order
+
+    static __device__ __forceinline__ void fetch(Fetched& v, const MxmArgs& g, int64_t row, int64_t step, int lane) {
+        const DFQ_GLOBAL float* x = (const DFQ_GLOBAL float*)g.a;
+        constexpr int n = mxl_part_len(FA);
+#pragma unroll
+        for (int part = 0; part < mxl_parts(FA); ++part) {
+            const int64_t k0 = mxl_part_k(FA, step, lane, part);
+            const DFQ_GLOBAL float* p = x + mxl_x_offset(row < g.M ? row : 0, k0 < g.K ? k0 : 0, g.lda);   // never past the array
+#pragma unroll
+            for (int q = 0; q < n; q += 4) {
+                float* o = &v[n * part + q];
+                if (VEC) {
+                    f32x4 t = {0.f, 0.f, 0.f, 0.f};
+                    if (mxl_reads(row, g.M, k0 + q, g.K)) t = *(const DFQ_GLOBAL f32x4*)(p + q);   // K % 4 == 0: all four exist
+                    o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) o[j] = mxl_reads(row, g.M, k0 + q + j, g.K) ? p[q + j] : 0.f;
+                }
+            }
+        }
+    }
+
+    static __device__ __forceinline__ void operand(mxg_v8i& a, int& s, const Fetched& v, const MxmArgs& g, int64_t row, int64_t step,
+                                                   int lane) {
+        uint32_t r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        int byte;
+        if (!mxg_hw_split(FA)) {
+            byte = mxl_scale_byte<FA>(mxl_part_amax<FA>(v, 0));
+            mxl_encode_part<FA>(r, v, 0, byte);
+        } else {
+            int b[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const uint32_t mine = mxl_part_amax<FA>(v, h), other = mxl_from_lane(mxl_split_partner(lane), mine);
+                b[h] = mxl_scale_byte<FA>(mine > other ? mine : other);
+                mxl_encode_part<FA>(r, v, h, b[h]);
+            }
+            const uint32_t w = mxl_from_lane(mxl_split_scale_lane(lane), (uint32_t)b[0] | ((uint32_t)b[1] << 8));
+            byte = (int)((w >> (8 * mxl_split_scale_byte(lane))) & 0xFFu);
+        }
+        s = mxg_lane_loads(row, g.M, mxg_lane_kblock(step, lane), g.nb) ? byte : 127;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) a[i] = (int)r[i];
+    }
+};
+
+// B's fragments of one K step: fragment j is instruction tile column j's.
+struct MxmB {
+    mxg_v8i b[kMxgSub];
+    int sb[kMxgSub];
+};
+
+template <class A, int FB>
+__device__ __forceinline__ void mxm_fetch(typename A::Fetched (&fa)[kMxgSub], MxmB& fb, const MxmArgs& g, int64_t m0, int64_t n0,
+                                          int64_t step, int lane) {
 #pragma unroll
     for (int i = 0; i < kMxgSub; ++i) {
-        mxg_load_operand<FA>(f.a[i], f.sa[i], g.a_codes, g.a_scales, mxg_lane_row(m0, i, lane), g.M, g.nb, step, lane);
-        mxg_load_operand<FB>(f.b[i], f.sb[i], g.b_codes, g.b_scales, mxg_lane_row(n0, i, lane), g.N, g.nb, step, lane);
+        if (!A::kAfterB) A::fetch(fa[i], g, mxg_lane_row(m0, i, lane), step, lane);
+        mxg_load_operand<FB>(fb.b[i], fb.sb[i], g.b_codes, g.b_scales, mxg_lane_row(n0, i, lane), g.N, g.nb, step, lane);
+    }
+    if (A::kAfterB) {
+#pragma unroll
+        for (int i = 0; i < kMxgSub; ++i) A::fetch(fa[i], g, mxg_lane_row(m0, i, lane), step, lane);
     }
 }
 
-// FA / FB: the instruction's format fields (cbsz / blgp) of A and B.
-template <int FA, int FB>
-__global__ __launch_bounds__(kThreads) void mx_gemm_kernel(const MxgArgs g) {
+// A: MxmStoredA or MxmFp32A.  A::F / FB: the instruction's format fields (cbsz / blgp) of A and B.
+template <class A, int FB>
+__global__ __launch_bounds__(kThreads) void mx_mm_kernel(const MxmArgs g) {
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const int64_t m0 = mxg_wave_m0(blockIdx.x, wave, g.N), n0 = mxg_wave_n0(blockIdx.x, wave, g.N);
     if (!mxg_wave_works(m0, n0, g.M, g.N)) return;   // wave-uniform; the kernel has no barrier
@@ -63,48 +244,55 @@ __global__ __launch_bounds__(kThreads) void mx_gemm_kernel(const MxgArgs g) {
 #pragma unroll
         for (int j = 0; j < kMxgSub; ++j) acc[i][j] = mxg_v4f{0.f, 0.f, 0.f, 0.f};
     const int64_t steps = mxg_steps(g.nb);
-    MxgFrags cur, nxt;
-    mxg_load<FA, FB>(cur, g, m0, n0, 0, lane);
+    typename A::Fetched fa[kMxgSub];
+    MxmB cur, nxt;
+    mxg_v8i a[kMxgSub];
+    int sa[kMxgSub];
+    mxm_fetch<A, FB>(fa, cur, g, m0, n0, 0, lane);
     for (int64_t s = 0; s < steps; ++s) {
-        if (s + 1 < steps) mxg_load<FA, FB>(nxt, g, m0, n0, s + 1, lane);
+#pragma unroll
+        for (int i = 0; i < kMxgSub; ++i) A::operand(a[i], sa[i], fa[i], g, mxg_lane_row(m0, i, lane), s, lane);
+        if (s + 1 < steps) mxm_fetch<A, FB>(fa, nxt, g, m0, n0, s + 1, lane);
 #pragma unroll
         for (int i = 0; i < kMxgSub; ++i)
 #pragma unroll
             for (int j = 0; j < kMxgSub; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(cur.a[i], cur.b[j], acc[i][j], FA, FB, 0,
-                                                                             cur.sa[i], 0, cur.sb[j]);
+                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[i], cur.b[j], acc[i][j], A::F, FB, 0, sa[i], 0,
+                                                                             cur.sb[j]);
         cur = nxt;
     }
-    DFQ_GLOBAL float* out = (DFQ_GLOBAL float*)g.out;
-    const DFQ_GLOBAL float* bias = (const DFQ_GLOBAL float*)g.bias;
-#pragma unroll
-    for (int j = 0; j < kMxgSub; ++j) {
-        const int64_t col = mxg_out_col(n0, j, lane);
-        const float bv = bias != nullptr && col < g.N ? bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < kMxgSub; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int64_t row = mxg_out_row(m0, i, lane, r);
-                if (!mxg_stores(row, col, g.M, g.N)) continue;
-                const float v = acc[i][j][r];
-                out[mxg_out_offset(row, col, g.ldo)] = bias != nullptr ? v + bv : v;
-            }
-    }
+    mxg_store_tile(acc, g.out, g.bias, g.ldo, g.M, g.N, m0, n0, lane);
 }
 
+// The launch of both entry points.  fp32: A is x (vec: on the 16-B path); otherwise stored codes.
 template <int FA, int FB>
-void mxg_launch(const MxgArgs& g, int64_t grid, hipStream_t s) {
-    hipLaunchKernelGGL((mx_gemm_kernel<FA, FB>), dim3((unsigned)grid), dim3(kThreads), 0, s, g);
+void mxm_launch(const MxmArgs& g, bool fp32, bool vec, int64_t grid, hipStream_t s) {
+    const dim3 blocks((unsigned)grid), threads(kThreads);
+    if (!fp32) hipLaunchKernelGGL((mx_mm_kernel<MxmStoredA<FA>, FB>), blocks, threads, 0, s, g);
+    else if (vec) hipLaunchKernelGGL((mx_mm_kernel<MxmFp32A<FA, true>, FB>), blocks, threads, 0, s, g);
+    else hipLaunchKernelGGL((mx_mm_kernel<MxmFp32A<FA, false>, FB>), blocks, threads, 0, s, g);
 }
 template <int FA>
-void mxg_launch_b(int fb, const MxgArgs& g, int64_t grid, hipStream_t s) {
+void mxm_launch_b(int fb, const MxmArgs& g, bool fp32, bool vec, int64_t grid, hipStream_t s) {
     switch (fb) {
-        case 0: return mxg_launch<FA, 0>(g, grid, s);
-        case 2: return mxg_launch<FA, 2>(g, grid, s);
-        case 3: return mxg_launch<FA, 3>(g, grid, s);
-        default: return mxg_launch<FA, 4>(g, grid, s);
+        case 0: return mxm_launch<FA, 0>(g, fp32, vec, grid, s);
+        case 2: return mxm_launch<FA, 2>(g, fp32, vec, grid, s);
+        case 3: return mxm_launch<FA, 3>(g, fp32, vec, grid, s);
+        default: return mxm_launch<FA, 4>(g, fp32, vec, grid, s);
     }
+}
+// fa / fb: mxg_hw_format of the two DFQ_MX_* formats (checked).
+int mxm_run(int fa, int fb, const MxmArgs& g, bool fp32, bool vec, int64_t grid, void* stream) {
+    static_assert(kMxgWaves * kWave == kThreads, "four waves per block");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (fa) {
+        case 0: mxm_launch_b<0>(fb, g, fp32, vec, grid, s); break;
+        case 2: mxm_launch_b<2>(fb, g, fp32, vec, grid, s); break;
+        case 3: mxm_launch_b<3>(fb, g, fp32, vec, grid, s); break;
+        default: mxm_launch_b<4>(fb, g, fp32, vec, grid, s); break;
+    }
+    DFQ_LAUNCH_CHECK();
+    return DFQ_OK;
 }
 
 }  // namespace
@@ -116,18 +304,17 @@ extern "C" int dfq_mx_gemm(const dfq_mx_gemm_desc* d, void* stream) {
     int64_t grid = 0;
     const int rc = mxg_check(d, grid);
     if (rc != DFQ_OK) return rc;
-    static_assert(kMxgWaves * kWave == kThreads, "four waves per block");
-    const MxgArgs g{static_cast<const uint8_t*>(d->a_codes), static_cast<const uint8_t*>(d->a_scales),
-                    static_cast<const uint8_t*>(d->b_codes), static_cast<const uint8_t*>(d->b_scales),
-                    d->bias, d->out, d->ldo, d->M, d->N, mxg_blocks(d->K)};
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int fb = mxg_hw_format(d->b_format);
-    switch (mxg_hw_format(d->a_format)) {
-        case 0: mxg_launch_b<0>(fb, g, grid, s); break;
-        case 2: mxg_launch_b<2>(fb, g, grid, s); break;
-        case 3: mxg_launch_b<3>(fb, g, grid, s); break;
-        default: mxg_launch_b<4>(fb, g, grid, s); break;
-    }
-    DFQ_LAUNCH_CHECK();
-    return DFQ_OK;
+    const MxmArgs g{d->a_codes, static_cast<const uint8_t*>(d->b_codes), static_cast<const uint8_t*>(d->b_scales), d->bias, d->out,
+                    0, d->ldo, d->M, d->N, d->K, mxg_blocks(d->K), static_cast<const uint8_t*>(d->a_scales)};
+    return mxm_run(mxg_hw_format(d->a_format), mxg_hw_format(d->b_format), g, false, false, grid, stream);
+}
+
+extern "C" int dfq_mx_linear(const dfq_mx_linear_desc* d, void* stream) {
+    int64_t grid = 0;
+    const int rc = mxl_check(d, grid);
+    if (rc != DFQ_OK) return rc;
+    const MxmArgs g{d->x, static_cast<const uint8_t*>(d->b_codes), static_cast<const uint8_t*>(d->b_scales), d->bias, d->out,
+                    d->ldx, d->ldo, d->M, d->N, d->K, mxg_blocks(d->K), nullptr};
+    const bool vec = mxl_vec(reinterpret_cast<uintptr_t>(d->x), d->ldx, d->K);
+    return mxm_run(mxg_hw_format(d->x_format), mxg_hw_format(d->b_format), g, true, vec, grid, stream);
 }

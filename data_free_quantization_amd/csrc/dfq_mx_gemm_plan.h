@@ -102,7 +102,33 @@ DFQ_HOST_DEVICE inline int64_t mxg_out_col(int64_t n0, int sub_n, int lane) { re
 DFQ_HOST_DEVICE inline bool mxg_stores(int64_t row, int64_t col, int64_t M, int64_t N) { return row < M && col < N; }
 DFQ_HOST_DEVICE inline int64_t mxg_out_offset(int64_t row, int64_t col, int64_t ldo) { return row * ldo + col; }
 
-// dfq_mx_gemm's argument checks (no device call); DFQ_OK and the grid, or the error.
+// The argument checks of dfq_mx_gemm and dfq_mx_linear (no device call), whose descriptors name
+// what they share alike: DFQ_OK and the grid, or the error.  A's part is the caller's: a_ok, its
+// pointers are there; a_hw, its format field; a_aligned, its base is; lda, the row stride of an
+// fp32 A -- K for stored codes, whose rows have no stride of their own, so that the checks of
+// lda pass whenever those of K do.
+template <class Desc>
+inline int mxm_check(const Desc& d, bool a_ok, int a_hw, bool a_aligned, int64_t lda, int64_t& grid) {
+    const auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    if (!a_ok || !d.b_codes || !d.b_scales || !d.out) return DFQ_ERR_INVALID;
+    if (a_hw < 0 || mxg_hw_format(d.b_format) < 0) return DFQ_ERR_INVALID;
+    if (d.flags != 0 || d.reserved != 0) return DFQ_ERR_INVALID;
+    if (d.M < 1 || d.N < 1 || d.K < 1) return DFQ_ERR_INVALID;
+    // byte and element offsets and the block count stay far inside int64 and the grid inside int32
+    if (d.M > (int64_t(1) << 31) || d.N > (int64_t(1) << 31) || d.K > (int64_t(1) << 40) ||
+        d.ldo > (int64_t(1) << 40) || lda > (int64_t(1) << 40))
+        return DFQ_ERR_INVALID;
+    if (d.M > (int64_t(1) << 50) / d.K || d.N > (int64_t(1) << 50) / d.K) return DFQ_ERR_INVALID;
+    if (lda < d.K || d.ldo < d.N) return DFQ_ERR_SHAPE;
+    if (d.M > (int64_t(1) << 50) / lda) return DFQ_ERR_INVALID;   // row * lda + k
+    if (!a_aligned || addr(d.b_codes) % mxg_code_align(d.b_format)) return DFQ_ERR_INVALID;
+    if (addr(d.out) % 4 || addr(d.bias) % 4) return DFQ_ERR_INVALID;
+    const int64_t g = mxg_grid(d.M, d.N);
+    if (g > 0x7fffffff) return DFQ_ERR_UNSUPPORTED;
+    grid = g;
+    return DFQ_OK;
+}
+
 int mxg_check(const dfq_mx_gemm_desc* d, int64_t& grid);
 
 }  // namespace dfq

@@ -1,4 +1,4 @@
-// The index arithmetic and the per-lane quantizer of dfq_mx_linear (dfq_mx_linear.hip):
+// The index arithmetic and the per-lane quantizer of dfq_mx_linear (dfq_mx_gemm.hip's fp32 A):
 // dfq_mx_gemm with the A operand built in the kernel from an fp32 activation.  Tiling, the B
 // operand, the accumulators and the stores are dfq_mx_gemm_plan.h's, unchanged; this header
 // adds which fp32 elements of x a lane reads, how it turns them into the operand registers and

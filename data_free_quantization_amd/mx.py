@@ -186,20 +186,17 @@ def _codes_arg(name: str, codes, scales, fmt: str, K: int):
     return rows
 
 
-def mx_gemm(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor,
-            b_fmt: str, K: int, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-            stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
-    """out[m, n] = sum_k A[m, k] * B[n, k] (+ bias[n]) on the scaled matrix instruction
-    (dfq_mx_gemm; DESIGN.md 3.8): A and B as the ``codes`` ([rows, nb, 16 | 24 | 32]
-    uint8) and ``scales`` ([rows, nb] uint8) ``mx_quantize`` writes for rows of K elements,
-    in any two formats.  ``out``: fp32 [M, N] whose rows may be strided (a column slice of
-    a wider tensor); allocated when None.  One launch, asynchronous on ``stream``."""
+def _k_arg(K) -> int:
     K = int(K)
     if K < 1:
         raise ValueError("K must be >= 1")
-    M = _codes_arg("a", a_codes, a_scales, a_fmt, K)
-    N = _codes_arg("b", b_codes, b_scales, b_fmt, K)
-    dev = a_codes.device
+    return K
+
+
+def _bias_out_args(what: str, M: int, N: int, dev, bias, out, others):
+    """The checks of ``bias`` and ``out`` of an mx_gemm / mx_linear_fused call (``what``) and of
+    every tensor's device (``others``: the operands besides the one ``dev`` is taken from);
+    ``out``, allocated when None."""
     if bias is not None:
         _lib.require_device(bias)
         if bias.numel() != N:
@@ -211,21 +208,44 @@ def mx_gemm(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: 
             raise TypeError("out: float32 on the GPU")
         if out.dim() != 2 or tuple(out.shape) != (M, N) or out.stride(1) != 1 or (M > 1 and out.stride(0) < N):
             raise ValueError("out must be [%d, %d] with unit column stride and a row stride >= %d" % (M, N, N))
-    for t in (a_scales, b_codes, b_scales, bias, out):
+    for t in (*others, bias, out):
         if t is not None and t.device != dev:
-            raise ValueError("every tensor of an mx_gemm call must live on one device")
-    d = _lib.MxGemmDesc()
-    d.a_codes, d.a_scales, d.b_codes, d.b_scales = (t.data_ptr() for t in (a_codes, a_scales, b_codes, b_scales))
+            raise ValueError("every tensor of an %s call must live on one device" % what)
+    return out
+
+
+def _multiply(entry: str, d, M: int, N: int, K: int, b_fmt: str, bias, out, stream, dev, tensors) -> torch.Tensor:
+    """What the two descriptors share filled in, the C call ``entry`` on ``stream`` (the
+    device's current one when None), and ``tensors`` kept alive for a stream of the caller's."""
     d.bias = bias.data_ptr() if bias is not None else None
     d.out, d.ldo = out.data_ptr(), (out.stride(0) if M > 1 else max(out.stride(0), N))
-    d.M, d.N, d.K, d.a_format, d.b_format = M, N, K, FORMATS[a_fmt][0], FORMATS[b_fmt][0]
+    d.M, d.N, d.K, d.b_format = M, N, K, FORMATS[b_fmt][0]
     s = C.c_void_p(stream.cuda_stream) if stream is not None else _lib.raw_stream(dev)
-    _lib.check(_lib.load().dfq_mx_gemm(C.byref(d), s), "dfq_mx_gemm", ValueError)
+    _lib.check(getattr(_lib.load(), entry)(C.byref(d), s), entry, ValueError)
     if stream is not None and stream != torch.cuda.current_stream(dev):
-        for t in (a_codes, a_scales, b_codes, b_scales, bias, out):
+        for t in (*tensors, bias, out):
             if t is not None:
                 t.record_stream(stream)
     return out
+
+
+def mx_gemm(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor,
+            b_fmt: str, K: int, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+            stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """out[m, n] = sum_k A[m, k] * B[n, k] (+ bias[n]) on the scaled matrix instruction
+    (dfq_mx_gemm; DESIGN.md 3.8): A and B as the ``codes`` ([rows, nb, 16 | 24 | 32]
+    uint8) and ``scales`` ([rows, nb] uint8) ``mx_quantize`` writes for rows of K elements,
+    in any two formats.  ``out``: fp32 [M, N] whose rows may be strided (a column slice of
+    a wider tensor); allocated when None.  One launch, asynchronous on ``stream``."""
+    K = _k_arg(K)
+    M = _codes_arg("a", a_codes, a_scales, a_fmt, K)
+    N = _codes_arg("b", b_codes, b_scales, b_fmt, K)
+    dev = a_codes.device
+    out = _bias_out_args("mx_gemm", M, N, dev, bias, out, (a_scales, b_codes, b_scales))
+    d = _lib.MxGemmDesc()
+    d.a_codes, d.a_scales, d.b_codes, d.b_scales = (t.data_ptr() for t in (a_codes, a_scales, b_codes, b_scales))
+    d.a_format = FORMATS[a_fmt][0]
+    return _multiply("dfq_mx_gemm", d, M, N, K, b_fmt, bias, out, stream, dev, (a_codes, a_scales, b_codes, b_scales))
 
 
 def mx_linear_fused(x: torch.Tensor, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str, K: int,
@@ -237,9 +257,7 @@ def mx_linear_fused(x: torch.Tensor, b_codes: torch.Tensor, b_scales: torch.Tens
     ``mx_quantize`` of x followed by ``mx_gemm``; the input's codes never reach memory.
     ``x`` needs unit column stride; any row stride >= K is passed on (a column slice of a wider
     tensor is read in place, no copy).  ``out`` as for ``mx_gemm``."""
-    K = int(K)
-    if K < 1:
-        raise ValueError("K must be >= 1")
+    K = _k_arg(K)
     if act_format not in FORMATS:
         raise ValueError("act_format must be %s, got %r" % (_NAMES, act_format))
     if b_fmt not in FORMATS:
@@ -257,34 +275,12 @@ def mx_linear_fused(x: torch.Tensor, b_codes: torch.Tensor, b_scales: torch.Tens
                          % (K, K, tuple(x.shape), tuple(x.stride())))
     M = x.shape[0]
     dev = x.device
-    if bias is not None:
-        _lib.require_device(bias)
-        if bias.numel() != N:
-            raise ValueError("bias holds %d elements, %d needed" % (bias.numel(), N))
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float32, device=dev)
-    else:
-        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32:
-            raise TypeError("out: float32 on the GPU")
-        if out.dim() != 2 or tuple(out.shape) != (M, N) or out.stride(1) != 1 or (M > 1 and out.stride(0) < N):
-            raise ValueError("out must be [%d, %d] with unit column stride and a row stride >= %d" % (M, N, N))
-    for t in (b_codes, b_scales, bias, out):
-        if t is not None and t.device != dev:
-            raise ValueError("every tensor of an mx_linear_fused call must live on one device")
+    out = _bias_out_args("mx_linear_fused", M, N, dev, bias, out, (b_codes, b_scales))
     d = _lib.MxLinearDesc()
     d.x, d.b_codes, d.b_scales = x.data_ptr(), b_codes.data_ptr(), b_scales.data_ptr()
-    d.bias = bias.data_ptr() if bias is not None else None
-    d.out = out.data_ptr()
     d.ldx = x.stride(0) if M > 1 else max(x.stride(0), K)
-    d.ldo = out.stride(0) if M > 1 else max(out.stride(0), N)
-    d.M, d.N, d.K, d.x_format, d.b_format = M, N, K, FORMATS[act_format][0], FORMATS[b_fmt][0]
-    s = C.c_void_p(stream.cuda_stream) if stream is not None else _lib.raw_stream(dev)
-    _lib.check(_lib.load().dfq_mx_linear(C.byref(d), s), "dfq_mx_linear", ValueError)
-    if stream is not None and stream != torch.cuda.current_stream(dev):
-        for t in (x, b_codes, b_scales, bias, out):
-            if t is not None:
-                t.record_stream(stream)
-    return out
+    d.x_format = FORMATS[act_format][0]
+    return _multiply("dfq_mx_linear", d, M, N, K, b_fmt, bias, out, stream, dev, (x, b_codes, b_scales))
 
 
 #: mx_linear calls since the last reset (utils.quantize.mx_matmul_forward resets it on entry)
@@ -317,24 +313,23 @@ def mx_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor
     _lib.require_device(x, weight, bias)
     if x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1] or x.shape[0] < 1 or x.shape[1] < 1:
         raise ValueError("x must be [M, K] and weight [N, K], got %s and %s" % (tuple(x.shape), tuple(weight.shape)))
-    if fused:
-        if weight_mx is None:
-            wi = mx_quantize([allocate(weight.detach(), weight_format, want_dst=False)], scale_search=weight_scale_search)[0]
-            weight_mx = (wi.codes, wi.scales)
-        LINEAR_CALLS += 1
-        return mx_linear_fused(x.detach(), weight_mx[0], weight_mx[1], weight_format, x.shape[1], act_format, bias=bias)
-    xi = allocate(x.detach(), act_format, want_dst=False)
+    # the weight's codes: given, or one mx_quantize call -- shared with the input's where both take
+    # the floor rule through the same entry point (not fused, no search)
+    xi = None if fused else allocate(x.detach(), act_format, want_dst=False)
     if weight_mx is None:
         wi = allocate(weight.detach(), weight_format, want_dst=False)
-        if weight_scale_search:   # two entry points: a call of its own
-            mx_quantize([xi])
-            mx_quantize([wi], scale_search=True)
+        if fused or weight_scale_search:
+            if xi is not None:
+                mx_quantize([xi])
+            mx_quantize([wi], scale_search=weight_scale_search)
         else:
             mx_quantize([xi, wi])
         weight_mx = (wi.codes, wi.scales)
-    else:
+    elif xi is not None:
         mx_quantize([xi])
     LINEAR_CALLS += 1
+    if fused:
+        return mx_linear_fused(x.detach(), weight_mx[0], weight_mx[1], weight_format, x.shape[1], act_format, bias=bias)
     return mx_gemm(xi.codes, xi.scales, act_format, weight_mx[0], weight_mx[1], weight_format, x.shape[1], bias=bias)
 
 

@@ -18,8 +18,12 @@ against the plain forward, for every activation format.  Data, not assertions.
 
   python scripts/mx_gemm_time.py          # -> profiles/r11/mx_gemm_time.jsonl
   python scripts/mx_gemm_time.py --sqnr   # -> profiles/r11/mx_forward_sqnr.jsonl
+  python scripts/mx_gemm_time.py --ab OTHER.so   # dfq_mx_gemm and dfq_mx_linear of another build of the library
+                                          #   (the parent commit's) against this tree's, alternated three
+                                          #   times in this process -> profiles/r14/mx_mm_parent_ab.jsonl
 """
 import argparse
+import ctypes as C
 import json
 import statistics
 import sys
@@ -84,6 +88,78 @@ def timing(args):
     emit(records, Path(args.out) if args.out else OUT / "mx_gemm_time.jsonl")
 
 
+def parent_ab(args):
+    """dfq_mx_gemm and dfq_mx_linear through two builds of the library in one process: --ab's
+    (the parent commit's, built into a scratch directory) and this tree's, alternated three
+    times on the same descriptors, so the same buffers.  dfq_mx_linear is timed on both of its
+    paths: x 16-B aligned (16-B loads) and the same x one float further (4-B loads).  The bound
+    of a (shape, pair, call) is the parent's own spread: the new median may exceed the parent's
+    median by no more than the parent's slowest leg exceeds its fastest.  The two builds' outputs
+    are compared for equality in every cell."""
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    _lib.preload()
+    stream = torch.cuda.current_stream(dev)
+    s = C.c_void_p(stream.cuda_stream)
+    mine, other = _lib.load(), C.CDLL(str(Path(args.ab).resolve()))
+    for name in ("dfq_mx_gemm", "dfq_mx_linear"):   # typed here: another commit's build need not export all this tree's binding asks for
+        getattr(other, name).argtypes, getattr(other, name).restype = getattr(mine, name).argtypes, getattr(mine, name).restype
+    libs = {"parent": other, "new": mine}
+    g = torch.Generator().manual_seed(0)
+    records = []
+    for name, M, N, K in SHAPES:
+        xbuf = torch.zeros(M * K + 4, device=dev)
+        xs = {"linear_16B": xbuf[:M * K].view(M, K), "linear_4B": xbuf[1:M * K + 1].view(M, K)}
+        for x in xs.values():
+            x.copy_(torch.randn(M, K, generator=g))
+        assert xs["linear_16B"].data_ptr() % 16 == 0 and xs["linear_4B"].data_ptr() % 16 == 4
+        w = (torch.randn(N, K, generator=g) * 0.05).to(dev)
+        bias = torch.randn(N, generator=g).to(dev)
+        out = torch.empty(M, N, device=dev)
+        for a_fmt, w_fmt in PAIRS:
+            xi, wi = mx.mx_quantize([mx.allocate(xs["linear_16B"], a_fmt, want_dst=False), mx.allocate(w, w_fmt, want_dst=False)])
+            dg = _lib.MxGemmDesc()
+            dg.a_codes, dg.a_scales, dg.b_codes, dg.b_scales = (t.data_ptr() for t in (xi.codes, xi.scales, wi.codes, wi.scales))
+            dg.bias, dg.out, dg.ldo, dg.M, dg.N, dg.K = bias.data_ptr(), out.data_ptr(), N, M, N, K
+            dg.a_format, dg.b_format = mx.FORMATS[a_fmt][0], mx.FORMATS[w_fmt][0]
+            calls = {"gemm": ("dfq_mx_gemm", dg)}
+            for kind, x in xs.items():
+                dl = _lib.MxLinearDesc()
+                dl.x, dl.b_codes, dl.b_scales, dl.bias, dl.out = (t.data_ptr() for t in (x, wi.codes, wi.scales, bias, out))
+                dl.ldx, dl.ldo, dl.M, dl.N, dl.K = K, N, M, N, K
+                dl.x_format, dl.b_format = mx.FORMATS[a_fmt][0], mx.FORMATS[w_fmt][0]
+                calls[kind] = ("dfq_mx_linear", dl)
+
+            def run(who, kind):
+                entry, d = calls[kind]
+                _lib.check(getattr(libs[who], entry)(C.byref(d), s), entry)
+
+            legs = []
+            for _ in range(3):
+                leg = {}
+                for kind in calls:
+                    for who in ("parent", "new"):
+                        leg["%s_%s_ms" % (who, kind)] = round(timed(lambda: run(who, kind), stream, args.warmup, args.steps), 5)
+                legs.append(leg)
+            rec = {"what": "dfq_mx_gemm / dfq_mx_linear: the parent commit's library against this tree's, alternated in one "
+                           "process on the same buffers", "shape": name, "M": M, "N": N, "K": K, "act_format": a_fmt,
+                   "weight_format": w_fmt, "device": torch.cuda.get_device_name(dev), "warmup": args.warmup,
+                   "steps": args.steps, "legs": legs}
+            for kind in calls:
+                run("parent", kind)
+                want = out.clone()
+                run("new", kind)
+                assert torch.equal(out.view(torch.int32), want.view(torch.int32)), (name, a_fmt, w_fmt, kind)
+                old = [leg["parent_%s_ms" % kind] for leg in legs]
+                new = [leg["new_%s_ms" % kind] for leg in legs]
+                rec[kind] = {"parent_ms": old, "new_ms": new, "parent_median": statistics.median(old),
+                             "new_median": statistics.median(new), "parent_spread": round(max(old) - min(old), 5),
+                             "new_within_parent_spread": statistics.median(new) <= statistics.median(old) + (max(old) - min(old))}
+            records.append(rec)
+    torch.cuda.synchronize()
+    emit(records, Path(args.out) if args.out else OUT.parent / "r14" / "mx_mm_parent_ab.jsonl")
+
+
 def sqnr(args):
     from data_free_quantization_amd import pipeline, zoo
     from data_free_quantization_amd.utils import layer_transform as L
@@ -128,6 +204,7 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--sqnr", action="store_true")
-    ap.add_argument("--out", default=None, help="the JSON lines' file (default: under profiles/r11)")
+    ap.add_argument("--ab", default=None, help="another build of libdfq_hip.so to time dfq_mx_gemm / dfq_mx_linear against")
+    ap.add_argument("--out", default=None, help="the JSON lines' file (default: under profiles/r11, --ab: profiles/r14)")
     a = ap.parse_args()
-    sqnr(a) if a.sqnr else timing(a)
+    sqnr(a) if a.sqnr else parent_ab(a) if a.ab else timing(a)

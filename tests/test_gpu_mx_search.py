@@ -14,11 +14,10 @@ import torch
 import torch.nn as nn
 
 from tests import mx_search_cases as SC
+from tests.mx_gpu_util import GB, GF, GUARD, as_bytes as _bytes, run
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-GUARD = 16   # elements after every output
-GF, GB = 12345.0, 0xA5
 
 
 @pytest.fixture(autouse=True)
@@ -29,54 +28,9 @@ def _linear_calls_back_at_zero():
     mx.reset_linear_calls()
 
 
-def _place(a, dev, off):
-    """``a`` on the device, starting ``off`` floats into a larger (aligned) buffer."""
-    buf = torch.full((a.size + 8 + GUARD,), GF, dtype=torch.float32, device=dev)
-    v = buf[off:off + a.size].view(a.shape)
-    v.copy_(torch.from_numpy(np.array(a)))   # a copy: the cases are read-only
-    assert v.is_contiguous() and v.data_ptr() % 16 == 4 * off
-    return buf, v
-
-
-def _items(cases, dev):
-    from data_free_quantization_amd import mx
-    items, bufs = [], []
-    for c in cases:
-        rows, row_len = c.x.shape
-        nb, cb = SC.blocks(row_len), SC.FORMATS[c.fmt][3]
-        co = c.code_offset
-        sbuf, src = _place(c.x, dev, c.offset)
-        b = {"src": sbuf}
-        it = mx.MXItem(src=src, fmt=c.fmt, khw=c.khw, rows=rows)
-        if c.outputs == "inplace":
-            it.dst, b["dst"] = src, sbuf
-        elif c.want_dst:
-            b["dst"] = torch.full((c.x.size + 8 + GUARD,), GF, dtype=torch.float32, device=dev)
-            it.dst = b["dst"][c.offset:c.offset + c.x.size].view(c.x.shape)
-        if c.want_codes:
-            b["codes"] = torch.full((co + rows * nb * cb + GUARD,), GB, dtype=torch.uint8, device=dev)
-            b["scales"] = torch.full((rows * nb + GUARD,), GB, dtype=torch.uint8, device=dev)
-            it.codes, it.scales = b["codes"][co:co + rows * nb * cb], b["scales"][:rows * nb]
-            assert it.codes.data_ptr() % 4 == co
-        if c.want_esum:
-            b["esum"] = torch.full((c.x.size // c.khw + GUARD,), GF, dtype=torch.float32, device=dev)
-            it.esum = b["esum"][:c.x.size // c.khw]
-        items.append(it)
-        bufs.append(b)
-    return items, bufs
-
-
 def _run(cases, scale_search=True):
-    """One call over ``cases``; every buffer back on the host, guards included."""
-    from data_free_quantization_amd import mx
-    items, bufs = _items(cases, torch.device(DEV))
-    mx.mx_quantize(items, scale_search=scale_search)
-    torch.cuda.synchronize()
-    return [{k: v.cpu().numpy() for k, v in b.items()} for b in bufs]
-
-
-def _bytes(out):
-    return {k: v.tobytes() for k, v in out.items()}
+    """One call over ``cases``, searched unless told otherwise; every buffer back on the host, guards included."""
+    return run(cases, scale_search=scale_search)
 
 
 def _check(c, out, ref=None):
