@@ -39,7 +39,7 @@ EXPORTS = [
     "dfq_pair_stats_ws_bytes", "dfq_pair_stats_batch",
     "dfq_clip_search_ws_bytes", "dfq_clip_search_batch",
     "dfq_mx_quantize_ws_bytes", "dfq_mx_quantize_batch", "dfq_mx_quantize_search_batch", "dfq_mx_gemm",
-    "dfq_mx_linear",
+    "dfq_mx_linear", "dfq_mx_conv2d",
 ]
 #: entry points only the diagnostics library exports (include/dfq_diag.h)
 DIAG_EXPORTS = ["dfq_probe_stream", "dfq_probe_lds", "dfq_debug_timeline", "dfq_debug_ablate",
@@ -132,6 +132,16 @@ class MxLinearDesc(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("b_codes", C.c_void_p), ("b_scales", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p),
         ("ldx", C.c_int64), ("ldo", C.c_int64), ("M", C.c_int64), ("N", C.c_int64), ("K", C.c_int64),
+        ("x_format", C.c_int32), ("b_format", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class MxConv2dDesc(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("b_codes", C.c_void_p), ("b_scales", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p),
+        ("B", C.c_int64), ("C", C.c_int64), ("H", C.c_int64), ("W", C.c_int64), ("N", C.c_int64), ("KH", C.c_int64),
+        ("KW", C.c_int64), ("stride_h", C.c_int64), ("stride_w", C.c_int64), ("pad_h", C.c_int64), ("pad_w", C.c_int64),
+        ("dil_h", C.c_int64), ("dil_w", C.c_int64),
         ("x_format", C.c_int32), ("b_format", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
     ]
 
@@ -230,6 +240,7 @@ def load(path: Optional[os.PathLike] = None) -> C.CDLL:
         "dfq_mx_quantize_search_batch": ([C.POINTER(MxDesc), I32, P, I64, P], C.c_int),
         "dfq_mx_gemm": ([C.POINTER(MxGemmDesc), P], C.c_int),
         "dfq_mx_linear": ([C.POINTER(MxLinearDesc), P], C.c_int),
+        "dfq_mx_conv2d": ([C.POINTER(MxConv2dDesc), P], C.c_int),
     }
     diag = {
         "dfq_probe_stream": ([P, P, P, P, I64, I32, P], C.c_int),

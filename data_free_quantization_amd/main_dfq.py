@@ -49,6 +49,13 @@ Same flags and stage order; the transforms run on the GPU.  Additive flags:
                        (mx.mx_linear_fused, dfq_mx_linear) instead of in a quantizer launch of its
                        own -- the same bits, one library launch per layer once its weight codes
                        are cached.  Needs --mx_matmul
+  --mx_matmul_conv     with --mx_matmul: every convolution with groups == 1 and zero padding mode --
+                       any kernel size, stride, padding and dilation -- multiplies on the scaled
+                       matrix instruction too (mx.mx_conv2d_fused, dfq_mx_conv2d): one launch reads
+                       the NCHW input in place, gathers each im2col row, rounds it in blocks of 32
+                       along (c, kh, kw) -- the order the weight's own MX blocks run in -- and
+                       stores NCHW.  Grouped and depthwise convolutions stay on fp32.  Needs
+                       --mx_matmul
 
 Example (README.md:137 of the reference):
   python -m data_free_quantization_amd.main_dfq --task cls --relu --equalize --absorption \
@@ -123,6 +130,9 @@ def get_argument(argv=None):
                         "rounded to this MX format")
     p.add_argument("--mx_matmul_fused", action="store_true",
                    help="with --mx_matmul: quantize each layer's input inside the multiply's kernel (one launch per layer)")
+    p.add_argument("--mx_matmul_conv", action="store_true",
+                   help="with --mx_matmul: k x k convolutions (groups == 1) multiply on the scaled matrix instruction too, "
+                        "their im2col rows gathered and rounded inside the kernel")
     p.add_argument("--mx_scale_search", action="store_true",
                    help="MX weights: per block, the better of the floor rule's scale and the next one up by "
                         "the block's own quantization noise")
@@ -131,6 +141,8 @@ def get_argument(argv=None):
         p.error("--mx_matmul needs an MX --weight_format")
     if args.mx_matmul_fused and args.mx_matmul is None:
         p.error("--mx_matmul_fused needs --mx_matmul")
+    if args.mx_matmul_conv and args.mx_matmul is None:
+        p.error("--mx_matmul_conv needs --mx_matmul")
     if args.mx_scale_search and args.weight_format == "int":
         p.error("--mx_scale_search needs an MX --weight_format")
     if args.weight_format != "int":
@@ -340,7 +352,7 @@ def main(argv=None):
         # bias fake-quant between batches (utils.quantize.frozen_weights)
         import contextlib
         from .utils.quantize import frozen_weights, mx_matmul_forward
-        scope = (mx_matmul_forward(args.mx_matmul, fused=args.mx_matmul_fused) if args.mx_matmul is not None
+        scope = (mx_matmul_forward(args.mx_matmul, fused=args.mx_matmul_fused, conv=args.mx_matmul_conv) if args.mx_matmul is not None
                  else contextlib.nullcontext())
         with frozen_weights(), scope:
             accuracy = inference_all(model, args.task, args)

@@ -283,6 +283,86 @@ def mx_linear_fused(x: torch.Tensor, b_codes: torch.Tensor, b_scales: torch.Tens
     return _multiply("dfq_mx_linear", d, M, N, K, b_fmt, bias, out, stream, dev, (x, b_codes, b_scales))
 
 
+def _pair(v, name: str):
+    """An int or a pair of ints as (h, w)."""
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise ValueError("%s: an int or a pair of ints, got %r" % (name, v))
+        return int(v[0]), int(v[1])
+    return int(v), int(v)
+
+
+def conv_out_size(size: int, k: int, stride: int, padding: int, dilation: int) -> int:
+    """Output extent of a convolution along one axis (< 1: the kernel does not fit)."""
+    span = size + 2 * padding - dilation * (k - 1) - 1
+    return span // stride + 1 if span >= 0 else 0
+
+
+def mx_conv2d_fused(x: torch.Tensor, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str, kernel_size, stride=1,
+                    padding=0, dilation=1, act_format: str = "mxfp8", bias: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """conv2d(Q(x), B) (+ bias) in one launch (dfq_mx_conv2d), groups == 1 and zero
+    padding: ``x`` fp32 contiguous NCHW [B, C, H, W], read in place; B the weight [N, C, KH, KW] as
+    the ``codes`` / ``scales`` ``mx_quantize`` writes for it -- rows of K = C * KH * KW elements,
+    blocks of 32 along (c, kh, kw).  The kernel gathers each im2col row, rounds it to ``act_format``
+    in blocks of 32 along the same (c, kh, kw) order (padding taps are +0 elements; the floor rule,
+    no scale search) and stores NCHW: bit for bit ``mx_linear_fused`` of the materialised
+    ``F.unfold`` matrix, without the matrix.  ``kernel_size``, ``stride``, ``padding``,
+    ``dilation``: ints or (h, w) pairs.  ``out``: fp32 contiguous [B, N, OH, OW]; allocated when
+    None.  Asynchronous on ``stream``."""
+    if act_format not in FORMATS:
+        raise ValueError("act_format must be %s, got %r" % (_NAMES, act_format))
+    if b_fmt not in FORMATS:
+        raise ValueError("b_fmt must be %s, got %r" % (_NAMES, b_fmt))
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x: a float32 tensor on the GPU")
+    if not x.is_cuda:
+        raise RuntimeError("data_free_quantization_amd multiplies MX codes on a ROCm GPU only; "
+                           "x is on %s (there is no CPU fallback)" % (x.device,))
+    if x.dtype != torch.float32:
+        raise TypeError("x: float32 on the GPU")
+    (KH, KW), (sh, sw) = _pair(kernel_size, "kernel_size"), _pair(stride, "stride")
+    (ph, pw), (dh, dw) = _pair(padding, "padding"), _pair(dilation, "dilation")
+    if min(KH, KW, sh, sw, dh, dw) < 1 or min(ph, pw) < 0:
+        raise ValueError("kernel_size, stride and dilation must be >= 1 and padding >= 0")
+    if x.dim() != 4 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError("x must be a contiguous [B, C, H, W] tensor, got %s with strides %s" % (tuple(x.shape), tuple(x.stride())))
+    B, Cin, H, W = x.shape
+    K = Cin * KH * KW
+    N = _codes_arg("b", b_codes, b_scales, b_fmt, K)
+    OH, OW = conv_out_size(H, KH, sh, ph, dh), conv_out_size(W, KW, sw, pw, dw)
+    if OH < 1 or OW < 1:
+        raise ValueError("the kernel %s (dilation %s) does not fit the padded input %s" % ((KH, KW), (dh, dw), (H + 2 * ph, W + 2 * pw)))
+    dev = x.device
+    if bias is not None:
+        _lib.require_device(bias)
+        if bias.numel() != N:
+            raise ValueError("bias holds %d elements, %d needed" % (bias.numel(), N))
+    if out is None:
+        out = torch.empty((B, N, OH, OW), dtype=torch.float32, device=dev)
+    else:
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32:
+            raise TypeError("out: float32 on the GPU")
+        if tuple(out.shape) != (B, N, OH, OW) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous [%d, %d, %d, %d] tensor" % (B, N, OH, OW))
+    for t in (b_codes, b_scales, bias, out):
+        if t is not None and t.device != dev:
+            raise ValueError("every tensor of an mx_conv2d_fused call must live on one device")
+    d = _lib.MxConv2dDesc()
+    d.x, d.b_codes, d.b_scales, d.out = x.data_ptr(), b_codes.data_ptr(), b_scales.data_ptr(), out.data_ptr()
+    d.bias = bias.data_ptr() if bias is not None else None
+    d.B, d.C, d.H, d.W, d.N, d.KH, d.KW = B, Cin, H, W, N, KH, KW
+    d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w = sh, sw, ph, pw, dh, dw
+    d.x_format, d.b_format = FORMATS[act_format][0], FORMATS[b_fmt][0]
+    s = C.c_void_p(stream.cuda_stream) if stream is not None else _lib.raw_stream(dev)
+    _lib.check(_lib.load().dfq_mx_conv2d(C.byref(d), s), "dfq_mx_conv2d", ValueError)
+    if stream is not None and stream != torch.cuda.current_stream(dev):
+        for t in (x, b_codes, b_scales, bias, out):
+            if t is not None:
+                t.record_stream(stream)
+    return out
+
+
 #: mx_linear calls since the last reset (utils.quantize.mx_matmul_forward resets it on entry)
 LINEAR_CALLS = 0
 

@@ -363,10 +363,11 @@ def frozen_weights():
 
 _MX_MATMUL = None   # the activation format of the open mx_matmul_forward() scope
 _MX_FUSED = False    # that scope multiplies through mx.mx_linear(fused=True)
+_MX_CONV = False     # that scope's convolutions multiply through mx.mx_conv2d_fused
 
 
 @contextlib.contextmanager
-def mx_matmul_forward(act_format: str = "mxfp8", fused: bool = False):
+def mx_matmul_forward(act_format: str = "mxfp8", fused: bool = False, conv: bool = False):
     """Inference with the MX layers' products on the scaled matrix instruction: inside
     this scope a Quant* layer whose ``weight_format`` mark (quantize_targ_layer's) is an MX
     format multiplies through ``mx.mx_linear`` -- its weight's MX codes times its input
@@ -381,17 +382,25 @@ def mx_matmul_forward(act_format: str = "mxfp8", fused: bool = False):
     ``fused``: the eligible layers multiply through ``mx.mx_linear(fused=True)`` -- the input is
     rounded inside the multiply's kernel (``dfq_mx_linear``), the same bits; inside
     ``frozen_weights()`` such a layer costs one library launch and no ``mx_quantize`` call after
-    its first forward."""
+    its first forward.
+    ``conv``: every QuantConv2d / QConv2d with groups == 1, padding_mode "zeros" and an int or
+    tuple padding -- any kernel size, stride and dilation -- multiplies through
+    ``mx.mx_conv2d_fused`` (``dfq_mx_conv2d``) on its NCHW input as it is: the im2col rows are
+    gathered and rounded inside the kernel, in blocks of 32 along (c, kh, kw), the order the
+    weight's own MX blocks run in, and the result is stored NCHW -- one launch, no permute, no
+    copy.  A pointwise layer gives the bits it gives with ``conv=False``.  Grouped and depthwise
+    convolutions, string padding and other padding modes stay on ``F.conv2d``; linear layers keep
+    following ``fused``."""
     from .. import mx
     if act_format not in mx.FORMATS:
         raise ValueError("act_format must be an MX format name, got %r" % (act_format,))
-    global _MX_MATMUL, _MX_FUSED
-    prev, _MX_MATMUL, _MX_FUSED = (_MX_MATMUL, _MX_FUSED), act_format, bool(fused)
+    global _MX_MATMUL, _MX_FUSED, _MX_CONV
+    prev, _MX_MATMUL, _MX_FUSED, _MX_CONV = (_MX_MATMUL, _MX_FUSED, _MX_CONV), act_format, bool(fused), bool(conv)
     mx.reset_linear_calls()
     try:
         yield
     finally:
-        _MX_MATMUL, _MX_FUSED = prev
+        _MX_MATMUL, _MX_FUSED, _MX_CONV = prev
 
 
 class _QuantWeightMixin:
@@ -410,10 +419,43 @@ class _QuantWeightMixin:
         fmt = self.__dict__.get("weight_format", "int")
         if _MX_MATMUL is None or fmt == "int":
             return None
-        if isinstance(self, nn.Conv2d) and not (tuple(self.kernel_size) == (1, 1) and self.groups == 1 and
-                                                 tuple(self.padding) == (0, 0)):
+        if isinstance(self, nn.Conv2d) and not self._mx_conv_routed() and not (
+                tuple(self.kernel_size) == (1, 1) and self.groups == 1 and tuple(self.padding) == (0, 0)):
             return None
         return fmt
+
+    def _mx_conv_routed(self):
+        """The convolution multiplies through mx.mx_conv2d_fused (mx_matmul_forward(conv=True))."""
+        return (_MX_CONV and self.groups == 1 and self.padding_mode == "zeros" and
+                not isinstance(self.padding, str))
+
+    def _mx_weight_codes(self, weight, bias, qweight, fmt):
+        """The (codes, scales) of the layer's weight viewed as [out, -1], kept in frozen_weights()."""
+        from .. import mx
+        key = self._weight_key(weight, bias)
+        search = bool(self.__dict__.get("mx_scale_search", False))
+        hit = self.__dict__.get("_mx_w_cache") if key is not None else None
+        if hit is None or hit[0] != (key, fmt, search):
+            w2d = qweight.reshape(qweight.shape[0], -1)
+            wi = mx.mx_quantize([mx.allocate(w2d.detach().contiguous(), fmt, want_dst=False)], scale_search=search)[0]
+            hit = ((key, fmt, search), wi.codes, wi.scales)
+            if key is not None:
+                self.__dict__["_mx_w_cache"] = hit
+            else:
+                self.__dict__.pop("_mx_w_cache", None)
+        return hit[1], hit[2]
+
+    def _mx_conv(self, input, weight, bias, qweight, qbias, fmt):
+        """The layer's product: mx.mx_conv2d_fused on the NCHW input (conv=True) or the 1x1 path."""
+        from .. import mx
+        if not self._mx_conv_routed():
+            return self._mx_conv1x1(input, weight, bias, qweight, qbias, fmt)
+        if not _no_autograd(input, weight, bias):
+            raise RuntimeError("mx_matmul_forward is an inference path: run it under torch.no_grad()")
+        codes, scales = self._mx_weight_codes(weight, bias, qweight, fmt)
+        mx.LINEAR_CALLS += 1
+        return mx.mx_conv2d_fused(input.detach().contiguous(), codes, scales, fmt, self.kernel_size, self.stride, self.padding,
+                                  self.dilation, act_format=_MX_MATMUL, bias=qbias)
 
     def _mx_product(self, x2d, weight, bias, qweight, qbias, fmt):
         """mx.mx_linear of the [rows, K] input with the layer's weight (its codes kept in frozen_weights())."""
@@ -498,7 +540,7 @@ class QuantConv2d(_QuantWeightMixin, nn.Conv2d):
         qweight, qbias = self._qparams(self.weight, self.bias)
         fmt = self._mx_format()
         if fmt is not None:
-            return self._mx_conv1x1(input, self.weight, self.bias, qweight, qbias, fmt)
+            return self._mx_conv(input, self.weight, self.bias, qweight, qbias, fmt)
         return F.conv2d(input, qweight, qbias, self.stride, self.padding, self.dilation, self.groups)
 
 
@@ -585,7 +627,7 @@ class QConv2d(QuantConv2d):
         qweight, qbias = self._qparams(w, b)
         fmt = self._mx_format()
         if fmt is not None:
-            return self._mx_conv1x1(input, w, b, qweight, qbias, fmt)
+            return self._mx_conv(input, w, b, qweight, qbias, fmt)
         return F.conv2d(input, qweight, qbias, self.stride, self.padding, self.dilation, self.groups)
 
 

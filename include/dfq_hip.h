@@ -598,6 +598,59 @@ typedef struct dfq_mx_linear_desc {
 } dfq_mx_linear_desc;
 int dfq_mx_linear(const dfq_mx_linear_desc* d, void* stream);
 
+/* ---- MX convolution in one launch: dfq_mx_linear on the im2col rows, gathered in the kernel ----
+ * out[b][n][oh][ow] = sum_k Q(A)[m][k] * B[n][k] (+ bias[n]) with
+ *   m = (b * OH + oh) * OW + ow,  k = (c * KH + i) * KW + j,  M = B * OH * OW,  K = C * KH * KW,
+ *   A[m][k] = x[b][c][oh * stride_h - pad_h + i * dil_h][ow * stride_w - pad_w + j * dil_w],
+ *             +0 where that lies outside the image,
+ *   OH = (H + 2 pad_h - dil_h (KH - 1) - 1) / stride_h + 1  (OW alike).
+ * x is the fp32 NCHW activation, read in place: the im2col matrix A is never written.  B is
+ * the convolution's weight [N, C, KH, KW] as dfq_mx_quantize_batch stores it, rows of K
+ * elements with blocks of 32 along (c, kh, kw) -- dfq_mx_gemm's B.  Q is dfq_mx_linear's,
+ * applied to the rows of A: blocks of 32 along k, a partial last block padded with +0, the
+ * floor rule, no scale search; a padding tap is a +0 element of its block like any other, and
+ * a block that lies wholly in padding gets scale byte 0.  Each lane gathers the 32 elements
+ * of its operand with 4-B loads (the tap of the run's first k decomposed once per K step,
+ * then walked kw -> kh -> c with carries), encodes them with dfq_mx_linear's encoder and
+ * exchanges, and the result goes straight to NCHW: a lane's four accumulator registers are
+ * four consecutive m of one n, one 16-B store where they lie in one image.
+ * The result is bit for bit dfq_mx_linear applied to the materialised [M, K] matrix A, on
+ * all 16 (x_format, b_format) pairs: one accumulator per output element, the K steps in
+ * order, no split of K, no atomics, no workspace, no LDS, the bias one fp32 add.  Domain and
+ * reproducibility: dfq_mx_linear's.
+ * Asynchronous on `stream`, no host wait.  Checked on the host before any device call:
+ * DFQ_ERR_INVALID for a NULL x, b_codes, b_scales or out, an unknown format, non-zero flags
+ * or reserved, an extent (B, C, H, W, N, KH, KW), stride or dilation < 1, a padding < 0, any
+ * of these above 2^28, C * H * W, N * OH * OW or K at or above 2^31, M above 2^31, N * K
+ * above 2^50 (so every offset stays inside int64 and the offsets inside one image inside
+ * int32), x, out or bias not 4-B aligned, b_codes not 16-B (FP6: 8-B) aligned;
+ * DFQ_ERR_SHAPE when OH or OW comes out < 1; DFQ_ERR_UNSUPPORTED for a grid beyond int32. */
+typedef struct dfq_mx_conv2d_desc {
+    const float* x;         /* fp32 [B, C, H, W], contiguous; 4-B aligned */
+    const void*  b_codes;   /* uint8 [N, nb, cb(b_format)], nb = ceil(K / 32), as dfq_mx_gemm's B */
+    const void*  b_scales;  /* uint8 [N, nb] */
+    const float* bias;      /* [N] or NULL */
+    float*       out;       /* fp32 [B, N, OH, OW], contiguous */
+    int64_t      B;
+    int64_t      C;
+    int64_t      H;
+    int64_t      W;
+    int64_t      N;
+    int64_t      KH;
+    int64_t      KW;
+    int64_t      stride_h;
+    int64_t      stride_w;
+    int64_t      pad_h;
+    int64_t      pad_w;
+    int64_t      dil_h;
+    int64_t      dil_w;
+    int32_t      x_format;  /* the MX format the im2col rows are rounded to (DFQ_MX_*) */
+    int32_t      b_format;
+    int32_t      flags;     /* 0 */
+    int32_t      reserved;  /* 0 */
+} dfq_mx_conv2d_desc;
+int dfq_mx_conv2d(const dfq_mx_conv2d_desc* d, void* stream);
+
 /* ---- high-bias absorption (bias_absorption.py:147-197) ------------------
  * c = max(bn_b - N*bn_w, 0) (bn_* = the BN's fake_weight / fake_bias);
  * b2[o] += sum_i (sum_k W2[o,i,k]) * c[g*i2 + i];  b1 -= c;  bn_b -= c.
