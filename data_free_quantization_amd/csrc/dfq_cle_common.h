@@ -1,5 +1,5 @@
 // Device helpers shared by the per-relation CLE kernels (dfq_cle_relation.hip)
-// and the device-resident loop (dfq_cle.hip): Cross_layer_equal.py:11-59.
+// and the device-resident loop (dfq_cle_kernels.h): Cross_layer_equal.py:11-59.
 #pragma once
 #include "dfq_common.h"
 

@@ -1,6 +1,7 @@
 // The CLE loop's planner: from the relations' and targets' shapes and tensor
 // identities to the tables of the device-resident loop (dfq_cle.hip) -- chains and
-// steps, rescale / range tasks, metric chunks and units, the lagged placement --
+// steps, rescale / range tasks, metric chunks and units, the lagged placement, and
+// the facts the launches derive from them (which step kernel, how many tiled chunks) --
 // in phases that each take and return a small struct.  Plain C++: no device
 // memory, no HIP call (the addresses are only compared), so it also builds and
 // runs on its own (tests/native/cle_plan_check.cpp).
@@ -587,6 +588,11 @@ int cle_build_structure(std::vector<CleRel> R, int64_t M, float* const* targets,
     S.nlaunch = P.nlaunch;
     S.stop_off = P.stop_off;
     S.lagged = P.lagged;
+    S.step_pos.assign(std::max<int32_t>(S.steps, 1), 0);
+    for (int32_t k = 0; k < S.steps; ++k)
+        for (int64_t t = S.astep[k]; t < S.astep[k + 1]; ++t)
+            if (S.at[t].kind == kApplyW2Tile && S.R[S.at[t].rel].khw2 > 1) S.step_pos[k] = 1;
+    for (const CleChunk& c : S.chunks) S.nbig += c.len >= 8 ? 1 : 0;
     S.id = ++g_struct_ids;
     cle_bytes(S);
     const double tp5 = now_us();
@@ -725,6 +731,8 @@ static uint64_t cle_structure_digest(const CleStructure& S) {
 //    relation, rows / channels / columns inside that relation's shapes;
 //  * range words and rollback saves: moff + 2 c1 <= M (both parities' words) and
 //    2 moff + 4 c1 <= 2 M (vsave: b1 | bn_w | bn_b | S per channel);
+//  * the facts the launches read: step_pos (which cle_loop_step_kernel a step
+//    launches) recomputed from the step's tasks, nbig from the chunks;
 //  * metric chunks and units: layer, element span, level-1 slots inside the tables;
 //  * placement: per launch offset the unit / range slices partition the tables;
 //    a tensor's tiles and ranges sit after its last rescale of iteration i and
@@ -801,8 +809,13 @@ extern "C" int dfq_diag_cle_check_structure(const dfq_cle_rel* rels, int32_t n_r
                     S.astep.empty() ? -1 : S.astep.back());
     std::vector<int32_t> rel_step(n_rel, -1);
     std::vector<std::pair<const float*, int32_t>> touch;   // (tensor, step) of every weight rescale
+    // which step kernel a step launches (cle_loop_step_kernel<POS>): recomputed from its tasks
+    if ((int32_t)S.step_pos.size() != std::max<int32_t>(steps, 1) || (steps == 0 && S.step_pos[0] != 0))
+        return fail("step_pos: %lld entries for %lld steps (first %lld)", (long long)S.step_pos.size(), steps,
+                    S.step_pos.empty() ? -1 : S.step_pos[0]);
     for (int32_t k = 0; k < steps; ++k) {
         if (S.astep[k + 1] < S.astep[k]) return fail("astep not monotone at step %lld: %lld > %lld", k, S.astep[k], S.astep[k + 1]);
+        bool pos = false;   // a W2 row tile with KH*KW > 1 in this step
         for (int64_t t = S.astep[k]; t < S.astep[k + 1]; ++t) {
             const CleTask& tk = S.at[t];
             if (tk.rel < 0 || tk.rel >= n_rel) return fail("rescale task %lld: relation %lld of %lld", t, tk.rel, n_rel);
@@ -826,6 +839,7 @@ extern "C" int dfq_diag_cle_check_structure(const dfq_cle_rel* rels, int32_t n_r
                     if (tk.b > c.o2 || tk.c0 < 0 || tk.c0 >= tk.c1 || tk.c1 > c.i2)
                         return fail("W2 tile task %lld: rows to %lld, columns to %lld", t, tk.b, tk.c1);
                     touch.push_back({c.w2, k});
+                    pos = pos || c.khw2 > 1;
                     break;
                 case kApplyChannels:
                     if (tk.b > c.c1) return fail("channel task %lld: channels to %lld of %lld", t, tk.b, c.c1);
@@ -837,6 +851,8 @@ extern "C" int dfq_diag_cle_check_structure(const dfq_cle_rel* rels, int32_t n_r
                     return fail("rescale task %lld: kind %lld", t, tk.kind, 0);
             }
         }
+        if ((S.step_pos[k] != 0) != pos)
+            return fail("step %lld: step_pos %lld, its tasks say %lld (the wrong step kernel)", k, S.step_pos[k], pos);
     }
     for (int32_t r = 0; r < n_rel; ++r)
         if (rel_step[r] < 0) return fail("relation %lld has no channel task", r, 0, 0);
@@ -853,7 +869,7 @@ extern "C" int dfq_diag_cle_check_structure(const dfq_cle_rel* rels, int32_t n_r
         if (!ok) return fail("range task %lld (kind %lld): span to %lld out of the relation's shape", t, tk.kind, tk.b);
     }
     // metric chunks and units
-    int64_t nb1_seen = 0;
+    int64_t nb1_seen = 0, nbig_seen = 0;   // level-1 slots; chunks with tiles (the stop rule's arrivals)
     for (size_t ci = 0; ci < S.chunks.size(); ++ci) {
         const CleChunk& ch = S.chunks[ci];
         if (ch.layer < 0 || ch.layer >= n_targets) return fail("chunk %lld: layer %lld of %lld", (long long)ci, ch.layer, n_targets);
@@ -862,8 +878,10 @@ extern "C" int dfq_diag_cle_check_structure(const dfq_cle_rel* rels, int32_t n_r
         const int64_t nb1 = ch.len / 32 / 256;
         if (S.b1off[ci] != 32 * nb1_seen) return fail("chunk %lld: level-1 offset %lld, expected %lld", (long long)ci, S.b1off[ci], 32 * nb1_seen);
         nb1_seen += nb1;
+        nbig_seen += ch.len >= 8 ? 1 : 0;
     }
     if (nb1_seen != S.nb1_total) return fail("level-1 slots %lld, table %lld", nb1_seen, S.nb1_total, 0);
+    if (nbig_seen != S.nbig) return fail("chunks with tiles %lld, nbig %lld", nbig_seen, S.nbig, 0);
     for (size_t u = 0; u < S.units.size(); ++u) {
         const CleUnit& un = S.units[u];
         if (un.chunk < 0 || un.chunk >= (int32_t)S.chunks.size()) return fail("unit %lld: chunk %lld", (long long)u, un.chunk, 0);

@@ -1,9 +1,10 @@
 // The CLE loop's planner (dfq_cle_plan.cpp): host-only code that turns the
 // relations' and targets' shapes and tensor identities into the tables the
-// device-resident loop (dfq_cle.hip) runs from.  This header holds what the planner
-// and the kernels share -- records, constants, index helpers -- and includes no HIP
-// header, so the planner builds as plain C++ (and on its own, under a sanitizer:
-// tests/native/cle_plan_check.cpp).
+// device-resident loop runs from (its host runtime: dfq_cle.hip; its kernels:
+// dfq_cle_kernels.h).  This header holds what the planner, the runtime and the
+// kernels share -- records, constants, index helpers, the structure a plan keeps --
+// and includes no HIP header, so the planner builds as plain C++ (and on its own,
+// under a sanitizer: tests/native/cle_plan_check.cpp).
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>
@@ -99,7 +100,7 @@ struct CleChunk {
     int64_t len;
 };
 
-// One metric tile (dfq_cle.hip, cle_tiles_body): kCleTile contiguous elements of a chunk
+// One metric tile (dfq_cle_kernels.h, cle_tiles_body): kCleTile contiguous elements of a chunk
 struct CleUnit {
     int32_t chunk;
     int32_t tile;     // < nb1: full level-1 tile; == nb1: the chunk's tail tile
@@ -130,7 +131,7 @@ constexpr int64_t kCleChansPerTask = 1024;
 constexpr int64_t kCleW1SmallElems = 2048, kCleDwRowsMult = 1;
 
 // W2 row tiles with KH*KW = khw in (1, kTileMaxKhw] and one group are rescaled
-// position-parallel (dfq_cle.hip, tile_by_position)
+// position-parallel (dfq_cle_kernels.h, tile_by_position)
 constexpr int kTileMaxKhw = 9;   // 3x3 (and 2x2); larger kernels keep the per-column walk
 // Rows per position-parallel rescale tile (<= kColTileRows): their loads are in
 // flight together (16-row tiles took ~70 us a task on ResNet-50's 3x3 layers,
@@ -155,8 +156,8 @@ struct CleSwitches {
 
 // Everything dfq_cle_plan_create derives from the relations' and targets' shapes
 // and tensor identities -- chains, steps, tasks, metric chunks and units, the
-// placement -- but no address: a plan of the same structure reuses it and binds
-// its own tensors (cle_structure_cached).
+// placement -- but no address: a plan of the same structure keeps a reference to
+// it, reads it at every launch and binds its own tensors (cle_structure_cached).
 struct CleStructure {
     std::vector<CleRel> R;   // fused / depthwise / self-range flags set (addresses: the first plan's)
     int64_t M = 0;
@@ -164,9 +165,14 @@ struct CleStructure {
     bool fused = false;
     std::vector<CleTask> rt, at;
     std::vector<int64_t> rstep, astep;   // task offsets per step (size steps + 1)
-    int64_t ri0 = 0, ri1 = 0;
+    // per step (size max(steps, 1)): it has W2 row tiles with KH*KW > 1, so its launch is
+    // cle_loop_step_kernel<true>, the instantiation with the position-parallel rescale
+    // (a wrong value launches the wrong kernel: the structure checker recomputes it)
+    std::vector<char> step_pos;
+    int64_t ri0 = 0, ri1 = 0;            // fused: each iteration's range tasks (the rest come from the rescales)
     std::vector<CleLayer> layers;   // n, nt (w / snap bound per plan)
     std::vector<CleChunk> chunks;
+    int64_t nbig = 0;               // chunks with tiles (len >= 8): the members of the stop rule's last arrival
     std::vector<CleUnit> units;
     std::vector<int64_t> b1off;
     int64_t nb1_total = 0;

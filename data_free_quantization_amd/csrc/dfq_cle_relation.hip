@@ -1,7 +1,7 @@
 // Cross-layer equalization, one relation at a time (Cross_layer_equal.py:11-59):
 // dfq_cle_relation (range kernels + rescale) and the dfq_diff_plan_* metric of
 // the host-driven loop (Cross_layer_equal.py:83,107-108).  The device-resident
-// loop (dfq_cle_plan_*) is in dfq_cle.hip.
+// loop (dfq_cle_plan_*): its host runtime is dfq_cle.hip, its kernels dfq_cle_kernels.h.
 #include "dfq_cle_common.h"
 
 #include <algorithm>

@@ -538,6 +538,12 @@ __host__ __device__ inline float aten_outer_col_sum(const float* a, int64_t R, i
 namespace dfq {
 void set_last_hip_error(hipError_t e);
 void set_last_hip_error_text(const char* msg);
+// msg (null: none) into dst[cap], cut to fit and always terminated
+inline void copy_error_text(char* dst, size_t cap, const char* msg) {
+    size_t i = 0;
+    for (; msg && msg[i] && i + 1 < cap; ++i) dst[i] = msg[i];
+    dst[i] = '\0';
+}
 // Stream-ordered host -> device upload of a host-built table (task lists, fold
 // jobs): `bytes` are copied into a pinned staging slot at once, the DMA is
 // enqueued on `s`, and the slot is reused only after an event recorded behind

@@ -9,19 +9,10 @@
 
 namespace dfq {
 static thread_local char g_last_hip[256] = "";
-void set_last_hip_error(hipError_t e) {
-    const char* msg = hipGetErrorString(e);
-    size_t i = 0;
-    for (; msg && msg[i] && i + 1 < sizeof(g_last_hip); ++i) g_last_hip[i] = msg[i];
-    g_last_hip[i] = '\0';
-}
+void set_last_hip_error(hipError_t e) { copy_error_text(g_last_hip, sizeof(g_last_hip), hipGetErrorString(e)); }
 // the calling thread's last HIP error text (a worker thread's error, reported by
 // the thread that joins it)
-void set_last_hip_error_text(const char* msg) {
-    size_t i = 0;
-    for (; msg && msg[i] && i + 1 < sizeof(g_last_hip); ++i) g_last_hip[i] = msg[i];
-    g_last_hip[i] = '\0';
-}
+void set_last_hip_error_text(const char* msg) { copy_error_text(g_last_hip, sizeof(g_last_hip), msg); }
 
 // Pinned staging slots for stage_h2d, per device (an event belongs to the device
 // it was created on).  A slot is free once the event recorded behind its last DMA

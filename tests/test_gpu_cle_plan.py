@@ -68,8 +68,9 @@ def _graph(seed, dead_dw=None):
     return g, rels
 
 
-def _replay(g, rels, s_min_max, thr, count, signed, eps):
-    """The reference loop with the oracle's _layer_equalization and metric."""
+def _replay(g, rels, s_min_max, thr, count, signed, eps, max_iters=None):
+    """The reference loop with the oracle's _layer_equalization and metric
+    (max_iters: the device loop's iteration cap, which the reference has not)."""
     tk = [k for k in g if type(g[k]) in (nn.Conv2d, nn.Linear)]
     W = {k: g[k].weight.detach().cpu().numpy().copy() for k in tk}
     B = {k: (g[k].bias.detach().cpu().numpy().copy() if g[k].bias is not None else None) for k in tk}
@@ -77,7 +78,7 @@ def _replay(g, rels, s_min_max, thr, count, signed, eps):
           for k in g if isinstance(g[k], _BN)}
     S = {}
     diff, it_count, diffs = 1e8, 0, []
-    while diff > thr and it_count < count:
+    while diff > thr and it_count < count and (max_iters is None or len(diffs) < max_iters):
         old = {k: W[k].copy() for k in tk}
         for i, r in enumerate(rels):
             a, b, bn = r.get_idxs()
@@ -121,6 +122,42 @@ def test_device_cle_matches_oracle(signed, eps, smm, thr, count, monkeypatch):
     # rescale) + that launch
     expect = 3 if fused else 5
     assert cle.LAST_RUN["launches_per_iteration"] == expect
+    assert cle.LAST_RUN["diffs"] == diffs
+    for k in W:
+        assert np.array_equal(g[k].weight.detach().cpu().numpy(), W[k]), k
+        if B[k] is not None:
+            assert np.array_equal(g[k].bias.detach().cpu().numpy(), B[k]), k
+    for k, (fw, fb) in BN.items():
+        if fw is not None:
+            assert np.array_equal(g[k].fake_weight.cpu().numpy(), fw), k
+            assert np.array_equal(g[k].fake_bias.cpu().numpy(), fb), k
+    for i, r in enumerate(rels):
+        assert np.array_equal(r.S.cpu().numpy(), S[i]), i
+
+
+@pytest.mark.parametrize("launch", [False, True])
+@pytest.mark.parametrize("cap", [1, 3])
+def test_device_cle_stops_at_iteration_cap(cap, launch, monkeypatch):
+    """The iteration cap (Cross_layer_equal.MAX_ITERS; the Python layer's default of
+    100,000 is never reached): the loop stops after `cap` iterations with the
+    warning, and weights, biases, BN fake statistics, S and diffs equal the oracle
+    replay cut at the same iteration, bit for bit.  The lagged schedule has by then
+    started iteration `cap` speculatively (its rescales run before the stop rule
+    of iteration cap - 1 is known), so this is the rollback's test; and cap + 1 <=
+    1025 keeps the history in the plan tables' own slots, not the context's buffer."""
+    from data_free_quantization_amd import Cross_layer_equal as cle
+    monkeypatch.setenv("DFQ_CLE_MODE", "device")
+    monkeypatch.setattr(cle, "MAX_ITERS", cap)
+    g, rels = _graph(0)
+    W, B, BN, S, diffs = _replay(g, rels, (1e-8, 1e8), 2e-7, 20, False, 0.0, max_iters=cap)
+    assert len(diffs) == cap   # the cap cut the loop short, not its stop rule
+    with pytest.warns(UserWarning, match="DFQ_CLE_MAX_ITERS"):
+        cle.cross_layer_equalization(g, rels, [nn.Conv2d, nn.Linear], Treshhold=2e-7, Count=20, Save_state=False,
+                                     launch=launch)
+        cle.wait()
+    torch.cuda.synchronize()
+    assert cle.LAST_RUN["launched"] == launch
+    assert cle.LAST_RUN["iterations"] == cap
     assert cle.LAST_RUN["diffs"] == diffs
     for k in W:
         assert np.array_equal(g[k].weight.detach().cpu().numpy(), W[k]), k
