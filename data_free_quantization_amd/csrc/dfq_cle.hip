@@ -61,7 +61,7 @@ struct CleTables {
         auto table = [&](auto*& ptr, int64_t count, bool host_built) {
             using T = std::remove_reference_t<decltype(*ptr)>;
             ptr = base ? reinterpret_cast<T*>(base + off) : nullptr;
-            off += ceil_div((int64_t)sizeof(T) * std::max<int64_t>(count, 1), (int64_t)256) * 256;
+            off += round256((int64_t)sizeof(T) * std::max<int64_t>(count, 1));
             if (host_built) host_bytes = off;   // (every host-built table comes before the first device-only one)
         };
         const int64_t nl = (int64_t)S.layers.size(), nch = (int64_t)S.chunks.size();
@@ -225,7 +225,7 @@ static void cle_plan_free(dfq_cle_plan* p) {
     delete p;
 }
 
-static int64_t snap_bytes(int64_t n) { return ceil_div(n * (int64_t)sizeof(float), (int64_t)256) * 256; }
+static int64_t snap_bytes(int64_t n) { return round256(n * (int64_t)sizeof(float)); }
 
 extern "C" int64_t dfq_cle_plan_ws_bytes(const int64_t* target_n, int32_t n_targets) {
     if (n_targets < 0 || (n_targets > 0 && !target_n)) return -1;

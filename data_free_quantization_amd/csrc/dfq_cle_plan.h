@@ -39,6 +39,8 @@ inline double now_us() {
 }
 
 DFQ_HOST_DEVICE inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// bytes up to the next multiple of 256: the alignment of every workspace part
+DFQ_HOST_DEVICE inline int64_t round256(int64_t b) { return ceil_div(b, (int64_t)256) * 256; }
 // at::native's CeilLog2 (the cascade's level step, dfq_common.h)
 DFQ_HOST_DEVICE inline int aten_ceil_log2(int64_t x) {
     if (x <= 2) return 1;

@@ -5,7 +5,6 @@
 
 namespace dfq {
 
-static int64_t round256(int64_t b) { return ceil_div(b, (int64_t)256) * 256; }
 
 static bool clip_ok(const dfq_clip_search_desc& p) {
     if (!p.w || reinterpret_cast<uintptr_t>(p.w) % 4) return false;

@@ -92,6 +92,32 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kWave));
     return v;
 }
+// (min, max) of a block of kThreads: every thread brings its (a, b); the waves'
+// results meet in smn / smx (kThreads / kWave floats each) and are combined in
+// wave order.  Thread 0 -- with kAll, every thread -- ends with the block's
+// result.  The caller puts a __syncthreads() before smn / smx are written again.
+template <bool kAll = false>
+__device__ __forceinline__ void block_minmax(float& a, float& b, float* smn, float* smx) {
+    a = wave_min(a);
+    b = wave_max(b);
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
+    if (lane == 0) {
+        smn[w] = a;
+        smx[w] = b;
+    }
+    __syncthreads();
+    if (kAll) {   // (thread 0 holds these already)
+        a = smn[0];
+        b = smx[0];
+    }
+    if (kAll || threadIdx.x == 0) {
+        for (int k = 1; k < kThreads / kWave; ++k) {
+            a = fminf(a, smn[k]);
+            b = fmaxf(b, smx[k]);
+        }
+    }
+}
+
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, kWave);
@@ -234,6 +260,21 @@ __device__ __forceinline__ float qdq_finish(float t, const QParams& p, float& q)
     const float y = q * p.s;
     return y + p.mn;
 }
+
+// scipy.stats.norm on an fp32 argument, in float64: pdf = exp(-x^2/2)/sqrt(2 pi);
+// cdf = cephes ndtr (erf below |x|/sqrt2 < 1/sqrt2, erfc above).
+__device__ __forceinline__ double ndtr_d(double a) {
+    const double x = a * 0.70710678118654752440;
+    const double z = fabs(x);
+    if (z < 0.70710678118654752440) return 0.5 + 0.5 * erf(x);
+    const double y = 0.5 * erfc(z);
+    return x > 0.0 ? 1.0 - y : y;
+}
+__device__ __forceinline__ float std_pdf(float x) {
+    const double xd = (double)x;
+    return (float)(exp(-(xd * xd) / 2.0) / 2.5066282746310002);
+}
+__device__ __forceinline__ float std_cdf(float x) { return (float)ndtr_d((double)x); }
 
 // ---------------------------------------------------------------------------
 // ATen's CPU fp32 summation order (at::native cascade_sum, SumKernel.cpp), which

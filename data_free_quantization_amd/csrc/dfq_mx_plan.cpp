@@ -4,7 +4,6 @@
 
 namespace dfq {
 
-static int64_t round256(int64_t b) { return ceil_div(b, (int64_t)256) * 256; }
 static uintptr_t addr(const void* p) { return reinterpret_cast<uintptr_t>(p); }
 
 static int mx_check(const dfq_mx_desc& p) {

@@ -4,7 +4,6 @@
 
 namespace dfq {
 
-static int64_t round256(int64_t b) { return ceil_div(b, (int64_t)256) * 256; }
 
 static bool pair_ok(const dfq_pair_desc& p) {
     if (!p.x || !p.y || (!p.rows_out && !p.total_out)) return false;

@@ -261,13 +261,12 @@ static int build(const dfq_tensor_desc* descs, int32_t n, SweepTables& B, const 
     return DFQ_OK;
 }
 
-static int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
 static PlanLayout plan_layout(const SweepTables& B) {
     PlanLayout L;
-    L.o_reduce = L.o_tensors + align256((int64_t)sizeof(DevTensor) * (int64_t)B.tensors.size());
-    L.o_main = L.o_reduce + align256((int64_t)sizeof(DevTask) * (int64_t)B.reduce.size());
-    L.o_slots = L.o_main + align256((int64_t)sizeof(DevTask) * (int64_t)B.main.size());
-    L.total = L.o_slots + align256((int64_t)sizeof(uint32_t) * 2 * B.slots);
+    L.o_reduce = L.o_tensors + round256((int64_t)sizeof(DevTensor) * (int64_t)B.tensors.size());
+    L.o_main = L.o_reduce + round256((int64_t)sizeof(DevTask) * (int64_t)B.reduce.size());
+    L.o_slots = L.o_main + round256((int64_t)sizeof(DevTask) * (int64_t)B.main.size());
+    L.total = L.o_slots + round256((int64_t)sizeof(uint32_t) * 2 * B.slots);
     return L;
 }
 

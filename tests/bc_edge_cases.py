@@ -28,7 +28,7 @@ import numpy as np
 THREADS = (1, 8, 16)
 PAR_NUMEL = 32768        # at::internal::GRAIN_SIZE: reductions below it run serially
 
-# limits of csrc/dfq_transform.hip the cases straddle
+# limits of csrc/dfq_bc.hip (dfq_transform_plan.h) the cases straddle
 K_BC_STAGE = 2048        # kBcStage: longest row / column the one-launch kernel stages
 K_BC_MAX_EXPECT = 4096   # kBcMaxExpect
 K_BC_MAX_TERMS = 8       # kBcMaxTerms

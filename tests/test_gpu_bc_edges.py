@@ -1,4 +1,4 @@
-"""The bias-correction kernels (csrc/dfq_transform.hip) against the REFERENCE's own
+"""The bias-correction kernels (csrc/dfq_bc.hip) against the REFERENCE's own
 results at the shapes where their reduction orders change
 (tests/golden/bc_edge_cases.npz, cases in tests/bc_edge_cases.py): bit for bit.
 

@@ -317,3 +317,80 @@ def test_bias_correction_returns_before_and_after_biases():
         assert torch.equal(v, b)
         changed += int(not torch.equal(v, entry[k]))
     assert changed > 0
+
+
+@pytest.mark.parametrize("rows,row_len", [(1, 1), (5, 9), (3, 1027)])
+def test_bn_fold_single_call_equals_the_batch(rows, row_len):
+    """dfq_bn_fold (one fold per call, two launches of its own kernels) against
+    dfq_bn_fold_batch of the same fold on copies of the same finite, normal inputs:
+    the weight, the bias, the four BN vectors and both fake statistics agree bit for
+    bit.  The last row's BN is the exact identity (weight 1, var 1, eps 0), which
+    the batch reads without rewriting."""
+    from data_free_quantization_amd import _lib
+    L = _lib.load()
+    rng = np.random.default_rng(1000 * rows + row_len)
+    w = (rng.standard_normal((rows, row_len)) * 0.2).astype(np.float32)
+    bias = rng.standard_normal(rows).astype(np.float32)
+    g = (rng.uniform(0.5, 1.5, rows) * rng.choice([-1.0, 1.0], rows)).astype(np.float32)
+    beta = rng.normal(0, 1, rows).astype(np.float32)
+    m = rng.normal(0, 0.3, rows).astype(np.float32)
+    v = rng.uniform(0.1, 3, rows).astype(np.float32)
+    g[-1], v[-1] = 1.0, 1.0
+    names = ("w", "bias", "g", "beta", "m", "v", "fake_w", "fake_b")
+    sets = [[T(a) for a in (w, bias, g, beta, m, v)] + [torch.full((rows,), 7.0, device=DEV) for _ in range(2)]
+            for _ in range(2)]
+    one, many = sets
+    s = _lib.stream_of(one[0])
+    _lib.check(L.dfq_bn_fold(*[t.data_ptr() for t in one], 0.0, rows, row_len, s), "dfq_bn_fold")
+    d = (_lib.BnFoldDesc * 1)()
+    for (field, _), t in zip(_lib.BnFoldDesc._fields_[:8], many):
+        setattr(d[0], field, t.data_ptr())
+    d[0].eps, d[0].flags, d[0].rows, d[0].row_len, d[0].range_enc = 0.0, 0, rows, row_len, None
+    need = int(L.dfq_bn_fold_ws_bytes(d, 1))
+    assert need > 0
+    ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+    _lib.check(L.dfq_bn_fold_batch(d, 1, ws.data_ptr(), need, s), "dfq_bn_fold_batch")
+    torch.cuda.synchronize()
+    for name, a, b in zip(names, one, many):
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32)), name
+    # and it folded: the identity row is untouched, the others are not, the BN is reset
+    got = one[0].cpu().numpy()
+    assert np.array_equal(got[-1], w[-1]) and (rows == 1 or not np.array_equal(got[0], w[0]))
+    assert np.array_equal(got, w * (g / np.sqrt(v))[:, None])
+    assert np.array_equal(one[6].cpu().numpy(), np.abs(g)) and np.array_equal(one[7].cpu().numpy(), beta)
+    assert all(np.array_equal(one[k].cpu().numpy(), np.full(rows, c, np.float32))
+               for k, c in ((2, 1.0), (3, 0.0), (4, 0.0), (5, 1.0)))
+
+
+@pytest.mark.parametrize("n", [1, 3, 4, 7, 1027])
+def test_clamp_single_call_equals_the_batch_and_torch(n):
+    """dfq_clamp against dfq_clamp_batch of one weight and torch.clamp, bit for bit:
+    the float4 body, the scalar tail and both together, on data that holds a -0.0
+    and (from three elements on) values on both sides of [lo, hi]; a weight that is
+    not 16-B aligned is DFQ_ERR_INVALID from both, and left alone."""
+    import ctypes as C
+    from data_free_quantization_amd import _lib
+    L = _lib.load()
+    lo, hi = -0.3, 0.4
+    x = torch.randn(n, generator=torch.Generator().manual_seed(n))
+    x[0] = -0.0
+    if n >= 3:
+        x[1], x[2] = -2.0, 2.0
+    want = torch.clamp(x, lo, hi)
+    one, many = x.to(DEV), x.to(DEV)
+    s = _lib.stream_of(one)
+    assert one.data_ptr() % 16 == 0 and many.data_ptr() % 16 == 0
+
+    def batch(t):
+        return L.dfq_clamp_batch((C.c_void_p * 1)(t.data_ptr()), (C.c_int64 * 1)(t.numel()), 1, lo, hi, s)
+    _lib.check(L.dfq_clamp(one.data_ptr(), n, lo, hi, s), "dfq_clamp")
+    _lib.check(batch(many), "dfq_clamp_batch")
+    torch.cuda.synchronize()
+    for got in (one, many):
+        assert torch.equal(got.cpu().view(torch.int32), want.view(torch.int32))
+    assert want.view(torch.int32)[0].item() == -2 ** 31        # the -0.0 is kept
+    buf = torch.full((n + 1,), 5.0, device=DEV)
+    assert L.dfq_clamp(buf[1:].data_ptr(), n, lo, hi, s) == _lib.DFQ_ERR_INVALID
+    assert batch(buf[1:]) == _lib.DFQ_ERR_INVALID
+    torch.cuda.synchronize()
+    assert torch.equal(buf.cpu(), torch.full((n + 1,), 5.0))
