@@ -55,20 +55,35 @@ __global__ void act_moments_kernel(const float* w_in, const float* b_in, int64_t
 
 // out = {min(a - N*w), max(a + N*w)} (get_min_value / get_max_value, :391-392);
 // w_is_var: w := sqrt(w + eps).  One block of kThreads.
+//
+// NaN: torch.min / torch.max propagate it (a variance that cancelled below -eps
+// makes torch.sqrt(var + eps) NaN, and the reference's range (nan, nan)), where
+// fminf / fmaxf drop it.  So a flag per output rides along, as in
+// observe_rows_kernel: a NaN among the a - N*w makes the min NaN, one among the
+// a + N*w the max.  Without a NaN the outputs keep fminf / fmaxf's bits.
 __global__ void __launch_bounds__(kThreads)
 act_minmax_kernel(const float* a, const float* w_in, int64_t n, int w_is_var, float eps, float nsig, float* out) {
     __shared__ float smn[kThreads / kWave], smx[kThreads / kWave];
+    __shared__ int snan[kThreads / kWave];
     float vmin = INFINITY, vmax = -INFINITY;
+    bool nan_lo = false, nan_hi = false;
     for (int64_t j = threadIdx.x; j < n; j += kThreads) {
         const float w = w_is_var ? sqrtf(w_in[j] + eps) : w_in[j];
         const float nw = nsig * w;
-        vmin = fminf(vmin, a[j] - nw);
-        vmax = fmaxf(vmax, a[j] + nw);
+        const float lo = a[j] - nw, hi = a[j] + nw;
+        vmin = fminf(vmin, lo);
+        vmax = fmaxf(vmax, hi);
+        nan_lo |= (lo != lo);
+        nan_hi |= (hi != hi);
     }
+    const int wnan = (__ballot(nan_lo) != 0 ? 1 : 0) | (__ballot(nan_hi) != 0 ? 2 : 0);
+    if ((threadIdx.x & (kWave - 1)) == 0) snan[threadIdx.x >> 6] = wnan;   // rides on block_minmax's barrier
     block_minmax(vmin, vmax, smn, smx);
     if (threadIdx.x == 0) {
-        out[0] = vmin;
-        out[1] = vmax;
+        int anynan = snan[0];
+        for (int q = 1; q < kThreads / kWave; ++q) anynan |= snan[q];
+        out[0] = (anynan & 1) ? __uint_as_float(0x7FC00000u) : vmin;
+        out[1] = (anynan & 2) ? __uint_as_float(0x7FC00000u) : vmax;
     }
 }
 

@@ -739,7 +739,9 @@ int dfq_bc_chain(const dfq_bc_op* ops, int32_t n_ops, int32_t* failed_op, void* 
 int dfq_act_moments(const float* w, const float* b, int64_t n, int32_t kind, int32_t sqrt_w, float eps,
                     int32_t accumulate, float* mean, float* var, void* stream);
 /* out2 = {min(a - nsig*w), max(a + nsig*w)} (get_min_value / get_max_value, :391-392),
- * w := sqrt(w + eps) when w_is_var.  out2: 2 device floats. */
+ * w := sqrt(w + eps) when w_is_var.  out2: 2 device floats.  NaN propagates as in
+ * torch.min / torch.max: one among the a - nsig*w makes out2[0] NaN, one among the
+ * a + nsig*w out2[1]. */
 int dfq_act_minmax(const float* a, const float* w, int64_t n, int32_t w_is_var, float eps, float nsig,
                    float* out2, void* stream);
 /* Case (d.) (:470-481): out[o] = sum_i (sum_k W[o,i,k]) * x[g*i2 + i] (+ bias[o]),

@@ -15,6 +15,8 @@ Outputs (all plain arrays, loadable with numpy allow_pickle=False):
                       bias_correction helpers on small layers
   bc_edge_cases.npz   the bias-correction helpers at the HIP kernels' reduction edges
                       (cases and inputs: tests/bc_edge_cases.py; section ``bc_edge``)
+  act_edge_cases.npz  set_quant_minmax on tiny add / case (d.) models, per channel, ReLU6
+                      and NaN included (tests/act_edge_cases.py; section ``act_edge``)
   pipeline_<model>.npz  main_dfq stage order on the synthetic models of
                       data_free_quantization_amd.zoo (positional graph keys)
 The synthetic model weights come from zoo.init_synthetic (numpy PCG64), so the
@@ -606,6 +608,74 @@ def act_ranges(name: str, seed: int = 0):
           str(A["bn1_error"]), str(A["bn2_error"]))
 
 
+def act_edge_cases():
+    """set_quant_minmax on the tiny traced models of tests/act_edge_cases.py ->
+    act_edge_cases.npz.  While it runs, torch.min / torch.max / torch.sqrt are
+    wrapped and their one-dimensional tensor arguments recorded: the reference's
+    per-channel mean - N*w, mean + N*w and var + eps (its lambdas are closures,
+    so what they compute is taken where it reaches torch).  Per graph: the
+    recorded vectors in call order (``seq`` indexes the file's pool of distinct
+    vectors, ``kinds`` says which function took each), every quantizer's
+    (min, max) and a digest of the inputs."""
+    from unittest import mock
+    import utils.layer_transform as ref_lt
+    from utils.quantize import QuantMeasure as RefQM
+    from data_free_quantization_amd.utils.layer_transform import CustomTensorOP as OurCTO
+    from tests import act_edge_cases as AE
+    AE.self_check()
+    A, pool, flat = {}, {}, []
+    for gname in AE.GRAPHS:
+        model = AE.build_model(gname)
+        A[f"{gname}.digest"] = np.array(h(AE.model_inputs(model)))
+        g = build_graph(model, "positional")
+        graph, bottoms = g.getGraph(), g.getBottoms()
+        tkeys = [k for k in graph if type(graph[k]) in TARG]
+        for k in tkeys:
+            graph[k].quant = RefQM(num_bits=8)
+        ops = OurCTO(graph, bottoms)
+        qms = [RefQM(num_bits=8) for _ in range(len(ops.quants))]
+        ref_lt.module_tensor_op = ref_lt.CustomTensorOP(qms, [(k, f"{k}_{ops.offsets[k][1]}") for k in ops.names])
+        ref_merge_bn(model, graph, bottoms, TARG)
+        rec = []
+
+        def spy(kind, real):
+            def wrapped(*a, **kw):
+                if len(a) == 1 and not kw and torch.is_tensor(a[0]) and a[0].dim() == 1:
+                    rec.append((kind, t2n(a[0])))
+                return real(*a, **kw)
+            return wrapped
+
+        with mock.patch.object(torch, "min", spy(AE.REC_MIN, torch.min)), \
+                mock.patch.object(torch, "max", spy(AE.REC_MAX, torch.max)), \
+                mock.patch.object(torch, "sqrt", spy(AE.REC_SQRT, torch.sqrt)):
+            ref_lt.set_quant_minmax(graph, bottoms, verbose=False)
+        seq = []
+        for _, v in rec:
+            key = v.tobytes()
+            if key not in pool:
+                pool[key] = len(flat)
+                flat.append(v)
+            seq.append(pool[key])
+        mods = [graph[k].quant for k in tkeys] + qms
+        A[f"{gname}.targets"] = np.array(tkeys, dtype=np.int64)
+        A[f"{gname}.op_keys"] = np.array(ops.names, dtype=np.str_)
+        A[f"{gname}.seq"] = np.array(seq, dtype=np.int32)
+        A[f"{gname}.kinds"] = np.array([k for k, _ in rec], dtype=np.uint8)
+        A[f"{gname}.min"] = np.array([float(q.running_min) for q in mods], dtype=np.float32)
+        A[f"{gname}.max"] = np.array([float(q.running_max) for q in mods], dtype=np.float32)
+        nans = sum(int(np.isnan(v).sum()) for _, v in rec)
+        if gname.startswith("clean."):
+            assert nans == 0 and np.isfinite(A[f"{gname}.min"]).all() and np.isfinite(A[f"{gname}.max"]).all(), gname
+        elif not gname.endswith("case_d"):   # the head's variance goes below -eps in >= 3 channels
+            assert int(np.isnan(rec[-1][1]).sum()) >= 3 and np.isnan(A[f"{gname}.min"][len(tkeys) - 1]), gname
+        print(gname, len(rec), "vectors recorded,", nans, "NaN elements")
+    ref_lt.module_tensor_op = None
+    A["pool_len"] = np.array([v.size for v in flat], dtype=np.int64)
+    A["pool"] = np.concatenate(flat)
+    np.savez_compressed(OUT / "act_edge_cases.npz", **A)
+    print("act edge cases:", len(AE.GRAPHS), "graphs,", len(flat), "distinct vectors")
+
+
 FWD_INPUT = {"mobilenetv2": (16, 3, 224, 224), "resnet50": (16, 3, 224, 224), "deeplab": (2, 3, 129, 129),
              "resnet18": (16, 3, 224, 224)}
 FWD_SEED = 2024
@@ -837,6 +907,8 @@ if __name__ == "__main__":
         transform_cases()
     if "bc_edge" in which:
         bc_edge_cases()
+    if "act_edge" in which:
+        act_edge_cases()
     for m in ("mobilenetv2", "resnet50", "deeplab", "resnet18"):
         if m in which:
             pipeline(m, per_channel=(m == "mobilenetv2"))

@@ -90,6 +90,25 @@ def bc_edge():
             "digest": dict(zip(names, digests))}
 
 
+@lru_cache(maxsize=1)
+def act_edge():
+    """tests/golden/act_edge_cases.npz by graph (tests/act_edge_cases.py GRAPHS):
+    {graph: {"rec": [(kind, vector), ...] in the reference's call order, "min",
+    "max" (every quantizer: target layers, then the tensor-op inputs), "targets",
+    "op_keys", "digest"}} (read-only arrays)."""
+    from tests import act_edge_cases as AE
+    z = np.load(GOLDEN / "act_edge_cases.npz", allow_pickle=False)
+    pool, ends = z["pool"], np.cumsum(z["pool_len"])
+    pool.setflags(write=False)
+    vec = [pool[e - n:e] for e, n in zip(ends, z["pool_len"])]
+    out = {}
+    for g in AE.GRAPHS:
+        out[g] = {"rec": [(int(k), vec[i]) for k, i in zip(z[f"{g}.kinds"], z[f"{g}.seq"])],
+                  "min": z[f"{g}.min"], "max": z[f"{g}.max"], "targets": list(z[f"{g}.targets"]),
+                  "op_keys": [str(k) for k in z[f"{g}.op_keys"]], "digest": str(z[f"{g}.digest"])}
+    return out
+
+
 def pipeline(name, threads=8, bits_weight=8):
     """The reference's main_dfq stage order on the synthetic model, run with
     ``threads`` torch intra-op threads (tests/golden/make_golden.py:pipeline);
