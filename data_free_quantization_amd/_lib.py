@@ -40,6 +40,7 @@ EXPORTS = [
     "dfq_clip_search_ws_bytes", "dfq_clip_search_batch",
     "dfq_mx_quantize_ws_bytes", "dfq_mx_quantize_batch", "dfq_mx_quantize_search_batch", "dfq_mx_gemm",
     "dfq_mx_linear", "dfq_mx_conv2d",
+    "dfq_int_gemm", "dfq_int_linear",
 ]
 #: entry points only the diagnostics library exports (include/dfq_diag.h)
 DIAG_EXPORTS = ["dfq_probe_stream", "dfq_probe_lds", "dfq_debug_timeline", "dfq_debug_ablate",
@@ -146,6 +147,26 @@ class MxConv2dDesc(C.Structure):
     ]
 
 
+class IntGemmDesc(C.Structure):
+    _fields_ = [
+        ("a_codes", C.c_void_p), ("a_scale", C.c_void_p), ("a_zero", C.c_void_p), ("b_codes", C.c_void_p),
+        ("b_scale", C.c_void_p), ("b_zero", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p),
+        ("ldo", C.c_int64), ("M", C.c_int64), ("N", C.c_int64), ("K", C.c_int64),
+        ("a_signed", C.c_int32), ("b_signed", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class IntLinearDesc(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("min_dev", C.c_void_p), ("max_dev", C.c_void_p), ("b_codes", C.c_void_p),
+        ("b_scale", C.c_void_p), ("b_zero", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p),
+        ("given_min", C.c_double), ("given_max", C.c_double),
+        ("ldx", C.c_int64), ("ldo", C.c_int64), ("M", C.c_int64), ("N", C.c_int64), ("K", C.c_int64),
+        ("x_bits", C.c_int32), ("x_symmetric", C.c_int32), ("b_signed", C.c_int32), ("flags", C.c_int32),
+        ("reserved", C.c_int32), ("reserved2", C.c_int32),
+    ]
+
+
 DFQ_BC_OP_EXPECT, DFQ_BC_OP_APPLY, DFQ_BC_OP_PROPAGATE, DFQ_BC_OP_COPY = 0, 1, 2, 3
 DFQ_BC_APPLY_VEC_SCRATCH = 1
 DFQ_BN_FOLD_ZERO_BIAS = 1
@@ -155,6 +176,7 @@ DFQ_MX_BLOCK = 32
 DFQ_MX_FP4_E2M1, DFQ_MX_FP8_E4M3 = 0, 1
 DFQ_MX_FP6_E2M3, DFQ_MX_FP6_E3M2 = 0x23, 0x32   # self-describing (exponent, mantissa bits): 2 stays invalid
 DFQ_MX_TASK_ELEMS, DFQ_MX_ESUM_TASK_ELEMS = 4096, 2048
+DFQ_INT_B_PACK4, DFQ_INT_B_PER_ROW, DFQ_INT_MAX_K = 0x1, 0x2, 32768
 
 _LIB: Optional[C.CDLL] = None
 
@@ -241,6 +263,8 @@ def load(path: Optional[os.PathLike] = None) -> C.CDLL:
         "dfq_mx_gemm": ([C.POINTER(MxGemmDesc), P], C.c_int),
         "dfq_mx_linear": ([C.POINTER(MxLinearDesc), P], C.c_int),
         "dfq_mx_conv2d": ([C.POINTER(MxConv2dDesc), P], C.c_int),
+        "dfq_int_gemm": ([C.POINTER(IntGemmDesc), P], C.c_int),
+        "dfq_int_linear": ([C.POINTER(IntLinearDesc), P], C.c_int),
     }
     diag = {
         "dfq_probe_stream": ([P, P, P, P, I64, I32, P], C.c_int),

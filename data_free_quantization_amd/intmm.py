@@ -1,0 +1,167 @@
+"""Integer matrix multiply on the i8 matrix instruction for the sweep's integer codes.
+
+Host wrappers of ``dfq_int_gemm`` and ``dfq_int_linear`` (include/dfq_hip.h):
+``int_gemm`` multiplies two operands given as the integer codes, scales and zeros the sweep
+(or ``utils.quantize.fake_quant``) writes -- uint8 / int8 bytes, or packed INT4 nibbles for
+B -- and ``int_linear`` multiplies an fp32 input, quantized inside the kernel by
+``fake_quant_given``'s quantizer, with such a B in one launch.  The integer sums are exact
+and the affine terms are applied in fp64 in a fixed order, so every output is bit for bit a
+numpy float64 statement (tests/int_gemm_cases.py).  There is no CPU fallback: CPU tensors
+raise."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import torch
+
+from . import _lib, mx
+
+MAX_K = _lib.DFQ_INT_MAX_K
+_CODE_DTYPES = (torch.uint8, torch.int8)
+
+
+def _on_gpu(name: str, t, what: str) -> None:
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s: %s on the GPU" % (name, what))
+    if not t.is_cuda:
+        raise RuntimeError("data_free_quantization_amd multiplies integer codes on a ROCm GPU only; "
+                           "%s is on %s (there is no CPU fallback)" % (name, t.device))
+
+
+def _codes_arg(name: str, codes, K: int, packed: bool = False) -> int:
+    """The checks of a code operand; its row count."""
+    _on_gpu(name, codes, "a uint8 or int8 tensor")
+    if codes.dtype not in _CODE_DTYPES or not codes.is_contiguous():
+        raise TypeError(name + ": contiguous uint8 or int8 on the GPU")
+    if packed and K % 2:
+        raise ValueError("packed codes need an even K (every row starts on a byte), got %d" % K)
+    row_bytes = K // 2 if packed else K
+    if codes.numel() < row_bytes or codes.numel() % row_bytes:
+        raise ValueError("%s holds %d bytes, no whole number of rows of %d" % (name, codes.numel(), row_bytes))
+    if codes.data_ptr() % 16:
+        raise ValueError(name + " must be 16-byte aligned")
+    return codes.numel() // row_bytes
+
+
+def _param_arg(name: str, t, counts, optional: bool = False):
+    """A scale or zero: fp32 on the GPU with one of ``counts`` elements."""
+    if t is None and optional:
+        return None
+    _on_gpu(name, t, "a float32 tensor")
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise TypeError(name + ": contiguous float32 on the GPU")
+    if t.numel() not in counts:
+        raise ValueError("%s holds %d values, %s needed" % (name, t.numel(), " or ".join(str(c) for c in counts)))
+    return t
+
+
+def _k_arg(K) -> int:
+    K = int(K)
+    if K < 1:
+        raise ValueError("K must be >= 1")
+    if K > MAX_K:
+        raise ValueError("K must be <= %d (the integer sums stay inside int32), got %d" % (MAX_K, K))
+    return K
+
+
+def _b_args(d, b_codes, b_scale, b_zero, K: int, b_packed: bool) -> int:
+    """B's checks and descriptor fields (shared by the two descriptors); N."""
+    N = _codes_arg("b_codes", b_codes, K, b_packed)
+    _param_arg("b_scale", b_scale, (1, N) if N > 1 else (1,))
+    _param_arg("b_zero", b_zero, (b_scale.numel(),), optional=True)
+    d.b_codes, d.b_scale = b_codes.data_ptr(), b_scale.data_ptr()
+    d.b_zero = b_zero.data_ptr() if b_zero is not None else None
+    d.b_signed = int(b_codes.dtype == torch.int8)
+    # N == 1: one value either way
+    d.flags |= (_lib.DFQ_INT_B_PACK4 if b_packed else 0) | (_lib.DFQ_INT_B_PER_ROW if b_scale.numel() > 1 else 0)
+    return N
+
+
+def _bias_out_args(what: str, d, M: int, N: int, K: int, dev, bias, out, others) -> torch.Tensor:
+    """mx.py's checks of ``bias``, ``out`` and the tensors' device; the descriptor fields both entries share."""
+    out = mx._bias_out_args(what, M, N, dev, bias, out, others)
+    d.bias = bias.data_ptr() if bias is not None else None
+    d.out, d.ldo = out.data_ptr(), (out.stride(0) if M > 1 else max(out.stride(0), N))
+    d.M, d.N, d.K = M, N, K
+    return out
+
+
+def int_gemm(a_codes: torch.Tensor, a_scale: torch.Tensor, a_zero: Optional[torch.Tensor], b_codes: torch.Tensor,
+             b_scale: torch.Tensor, b_zero: Optional[torch.Tensor], K: int, *, b_packed: bool = False,
+             bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[m, n] = sum_k (qa[m, k] * sa + za) * (qb[n, k] * sb[n] + zb[n]) (+ bias[n]) on the
+    i8 matrix instruction (dfq_int_gemm).  ``a_codes``: M * K bytes, ``b_codes``:
+    N * K bytes -- or N * K / 2 packed bytes with ``b_packed`` (the sweep's ``pack_int4`` layout,
+    K even) -- contiguous, rows of K elements; uint8 codes are unsigned and int8 codes signed
+    (packed nibbles are two's complement when the tensor is int8: view the sweep's packed
+    symmetric codes as int8).  ``a_scale`` / ``a_zero``: one fp32 value each; ``b_scale`` /
+    ``b_zero``: one value each, or N (per output channel); a zero may be None (0).  ``out``:
+    fp32 [M, N] whose rows may be strided; allocated when None.  The result is the contract's
+    fp64 statement bit for bit.  One launch, asynchronous on the current stream."""
+    K = _k_arg(K)
+    M = _codes_arg("a_codes", a_codes, K)
+    _param_arg("a_scale", a_scale, (1,))
+    _param_arg("a_zero", a_zero, (1,), optional=True)
+    d = _lib.IntGemmDesc()
+    N = _b_args(d, b_codes, b_scale, b_zero, K, bool(b_packed))
+    dev = a_codes.device
+    out = _bias_out_args("int_gemm", d, M, N, K, dev, bias, out, (a_scale, a_zero, b_codes, b_scale, b_zero))
+    d.a_codes, d.a_scale = a_codes.data_ptr(), a_scale.data_ptr()
+    d.a_zero = a_zero.data_ptr() if a_zero is not None else None
+    d.a_signed = int(a_codes.dtype == torch.int8)
+    _lib.check(_lib.load().dfq_int_gemm(C.byref(d), _lib.raw_stream(dev)), "dfq_int_gemm", ValueError)
+    return out
+
+
+#: int_linear calls since the last reset (utils.quantize.int_matmul_forward resets it on entry)
+LINEAR_CALLS = 0
+
+
+def reset_linear_calls() -> None:
+    global LINEAR_CALLS
+    LINEAR_CALLS = 0
+
+
+def int_linear(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor, b_zero: Optional[torch.Tensor], K: int, *,
+               bits: int = 8, symmetric: bool = False, min_dev: Optional[torch.Tensor] = None,
+               max_dev: Optional[torch.Tensor] = None, min_value=None, max_value=None, scale_f32: bool = False,
+               b_packed: bool = False, bias: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``int_gemm`` with A given as fp32 ``x`` [M, K] and quantized to ``bits`` (2..8) inside the
+    kernel (dfq_int_linear): the quantizer is ``fake_quant_given``'s -- the range from the
+    device scalars ``min_dev`` / ``max_dev`` (no host synchronisation) or the Python floats
+    ``min_value`` / ``max_value``, ``scale_f32`` as there -- and the codes of x never reach
+    memory.  Bit for bit ``fake_quant`` of x on that range (codes, scale, zero) followed by
+    ``int_gemm``.  ``x`` needs unit column stride; any row stride >= K is passed on (a column
+    slice of a wider tensor is read in place).  B, ``bias`` and ``out`` as for ``int_gemm``."""
+    global LINEAR_CALLS
+    K = _k_arg(K)
+    bits = int(bits)
+    if not 2 <= bits <= 8:
+        raise ValueError("bits must be 2..8, got %d" % bits)
+    _on_gpu("x", x, "a float32 tensor")
+    if x.dtype != torch.float32:
+        raise TypeError("x: float32 on the GPU")
+    if x.dim() != 2 or x.shape[1] != K or x.shape[0] < 1 or x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < K):
+        raise ValueError("x must be [M, %d] with unit column stride and a row stride >= %d, got %s with strides %s"
+                         % (K, K, tuple(x.shape), tuple(x.stride())))
+    d = _lib.IntLinearDesc()
+    for name, dev_v, host_v in (("min", min_dev, min_value), ("max", max_dev, max_value)):
+        if dev_v is not None:
+            _param_arg(name + "_dev", dev_v, (1,))
+        elif host_v is None:
+            raise ValueError("the range's %s is missing: pass %s_dev or %s_value" % (name, name, name))
+    d.min_dev = min_dev.data_ptr() if min_dev is not None else None
+    d.max_dev = max_dev.data_ptr() if max_dev is not None else None
+    d.given_min = float(min_value) if min_value is not None else 0.0
+    d.given_max = float(max_value) if max_value is not None else 0.0
+    d.flags = _lib.DFQ_SCALE_F32 if scale_f32 else 0
+    N = _b_args(d, b_codes, b_scale, b_zero, K, bool(b_packed))
+    M, dev = x.shape[0], x.device
+    out = _bias_out_args("int_linear", d, M, N, K, dev, bias, out, (min_dev, max_dev, b_codes, b_scale, b_zero))
+    d.x, d.ldx = x.data_ptr(), (x.stride(0) if M > 1 else max(x.stride(0), K))
+    d.x_bits, d.x_symmetric = bits, int(bool(symmetric))
+    _lib.check(_lib.load().dfq_int_linear(C.byref(d), _lib.raw_stream(dev)), "dfq_int_linear", ValueError)
+    LINEAR_CALLS += 1
+    return out

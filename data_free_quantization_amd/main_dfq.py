@@ -56,6 +56,14 @@ Same flags and stage order; the transforms run on the GPU.  Additive flags:
                        along (c, kh, kw) -- the order the weight's own MX blocks run in -- and
                        stores NCHW.  Grouped and depthwise convolutions stay on fp32.  Needs
                        --mx_matmul
+  --int_matmul         run the evaluation's Linear and 1x1-convolution products on the i8 matrix
+                       instruction (utils.quantize.int_matmul_forward, intmm.int_linear,
+                       dfq_int_linear): the layer's per-tensor integer weight codes times its
+                       input's activation codes, re-derived inside the kernel from the
+                       fake-quantized input and the observer's range -- what an integer
+                       deployment of the quantized model computes, integer sums exact, the
+                       affine terms in fp64.  k x k, grouped and depthwise convolutions stay on
+                       fp32.  Needs --quantize and --weight_format int; not with --mx_matmul
 
 Example (README.md:137 of the reference):
   python -m data_free_quantization_amd.main_dfq --task cls --relu --equalize --absorption \
@@ -133,6 +141,9 @@ def get_argument(argv=None):
     p.add_argument("--mx_matmul_conv", action="store_true",
                    help="with --mx_matmul: k x k convolutions (groups == 1) multiply on the scaled matrix instruction too, "
                         "their im2col rows gathered and rounded inside the kernel")
+    p.add_argument("--int_matmul", action="store_true",
+                   help="evaluate with the integer layers' Linear and 1x1-convolution products on the i8 matrix "
+                        "instruction, from the weight and activation codes")
     p.add_argument("--mx_scale_search", action="store_true",
                    help="MX weights: per block, the better of the floor rule's scale and the next one up by "
                         "the block's own quantization noise")
@@ -143,6 +154,10 @@ def get_argument(argv=None):
         p.error("--mx_matmul_fused needs --mx_matmul")
     if args.mx_matmul_conv and args.mx_matmul is None:
         p.error("--mx_matmul_conv needs --mx_matmul")
+    if args.int_matmul and args.mx_matmul is not None:
+        p.error("--int_matmul conflicts with --mx_matmul")
+    if args.int_matmul and (not args.quantize or args.weight_format != "int"):
+        p.error("--int_matmul needs --quantize and --weight_format int")
     if args.mx_scale_search and args.weight_format == "int":
         p.error("--mx_scale_search needs an MX --weight_format")
     if args.weight_format != "int":
@@ -351,9 +366,9 @@ def main(argv=None):
         # the weights are final from here: the Quant* layers keep their weight /
         # bias fake-quant between batches (utils.quantize.frozen_weights)
         import contextlib
-        from .utils.quantize import frozen_weights, mx_matmul_forward
+        from .utils.quantize import frozen_weights, int_matmul_forward, mx_matmul_forward
         scope = (mx_matmul_forward(args.mx_matmul, fused=args.mx_matmul_fused, conv=args.mx_matmul_conv) if args.mx_matmul is not None
-                 else contextlib.nullcontext())
+                 else int_matmul_forward() if args.int_matmul else contextlib.nullcontext())
         with frozen_weights(), scope:
             accuracy = inference_all(model, args.task, args)
         print(f"Inference time is {time.time() - start} seconds")

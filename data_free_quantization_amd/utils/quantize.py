@@ -290,7 +290,9 @@ class QuantMeasure(nn.Module):
             # async launch (the reference's main_dfq runs its observers in training
             # mode at inference -- set_layer_bits makes new ones -- so both branches)
             input.shape[0]   # the reference's quantize() indexes shape[0]
+            self.__dict__["_given_range"] = (mn, mx)   # int_matmul_forward's layers re-derive the codes from it
             return fake_quant_given(input, self.num_bits, min_dev=mn, max_dev=mx)
+        self.__dict__["_given_range"] = None
         return quantize(input, self.num_bits, min_value=float(mn), max_value=float(mx), num_chunks=16)
 
     def _forward_fused(self, input):
@@ -323,7 +325,9 @@ class QuantMeasure(nn.Module):
                                                float(self.momentum), _lib.ptr(out2), stream),
                    "dfq_act_observe", RuntimeError)
         if _no_autograd(input):
+            self.__dict__["_given_range"] = (out2[0], out2[1])
             return fake_quant_given(input, self.num_bits, min_dev=out2[0], max_dev=out2[1])
+        self.__dict__["_given_range"] = None
         mn, mx = out2.tolist()   # the STE path: the reference's float(mn) / float(mx)
         return quantize(input, self.num_bits, min_value=mn, max_value=mx, num_chunks=16)
 
@@ -401,6 +405,38 @@ def mx_matmul_forward(act_format: str = "mxfp8", fused: bool = False, conv: bool
         yield
     finally:
         _MX_MATMUL, _MX_FUSED, _MX_CONV = prev
+
+
+_INT_MATMUL = False   # an int_matmul_forward() scope is open
+
+
+@contextlib.contextmanager
+def int_matmul_forward():
+    """Inference with the integer layers' products on the i8 matrix instruction: inside this
+    scope a Quant* layer whose ``weight_format`` mark is "int" (the default) multiplies through
+    ``intmm.int_linear`` -- its weight's integer codes times its input's activation codes --
+    instead of ``F.linear`` / ``F.conv2d`` on the dequantized fp32 tensors.  Eligible, with
+    weight and activation grids of at most 8 bits: QuantLinear / QLinear, and QuantConv2d /
+    QConv2d with a 1x1 kernel, groups == 1 and zero padding (a stride slices the input).
+    The weight's codes, scale and zero come from ``fake_quant(weight, num_bits)``: per tensor,
+    asymmetric, on its own range -- the grid the plain forward's weight fake quant puts it on;
+    inside ``frozen_weights()`` they are kept under the weight cache's key.  The activation
+    fake quant runs unchanged; the layer hands its output, and the device pair (min, max) the
+    observer quantized it with, to the kernel, which quantizes it again on that range (no host
+    synchronisation).  That gives back the codes the fake quant chose while
+    max(|min|, |max|) <= 0.99 * 2^23 / (2^bits - 1) * (max - min) -- 2^15 (max - min) at 8
+    bits; beyond it a code may move by one.  The bias fake quant stays and is
+    added in the kernel.  k x k, grouped and depthwise convolutions, MX layers and everything
+    outside the scope are untouched.  The scope resets ``intmm.LINEAR_CALLS``.  An inference
+    path: under autograd the layers raise."""
+    from .. import intmm
+    global _INT_MATMUL
+    prev, _INT_MATMUL = _INT_MATMUL, True
+    intmm.reset_linear_calls()
+    try:
+        yield
+    finally:
+        _INT_MATMUL = prev
 
 
 class _QuantWeightMixin:
@@ -485,6 +521,48 @@ class _QuantWeightMixin:
         x2d = input.reshape(-1, input.shape[-1]).contiguous()
         return self._mx_product(x2d, weight, bias, qweight, qbias, fmt).view(*input.shape[:-1], -1)
 
+    def _int_routed(self):
+        """The layer's product runs through intmm.int_linear (int_matmul_forward)."""
+        if not _INT_MATMUL or self.__dict__.get("weight_format", "int") != "int":
+            return False
+        if self.num_bits > 8 or self.quant.num_bits > 8:
+            return False
+        if isinstance(self, nn.Conv2d):
+            return (tuple(self.kernel_size) == (1, 1) and self.groups == 1 and not isinstance(self.padding, str) and
+                    tuple(self.padding) == (0, 0))
+        return True
+
+    def _int_product(self, x2d, weight, bias, qbias):
+        """intmm.int_linear of the fake-quantized [rows, K] input with the weight's integer codes
+        (kept in frozen_weights()), on the range the observer just quantized the input with."""
+        from .. import intmm
+        rng = self.quant.__dict__.get("_given_range")
+        if rng is None or not _no_autograd(x2d, weight, bias):
+            raise RuntimeError("int_matmul_forward is an inference path: run it under torch.no_grad()")
+        key = self._weight_key(weight, bias)
+        hit = self.__dict__.get("_int_w_cache") if key is not None else None
+        if hit is None or hit[0] != key:
+            w2d = weight.detach().reshape(weight.shape[0], -1).contiguous()
+            r = fake_quant(w2d, self.num_bits, per_channel=False, symmetric=False)
+            hit = (key, r.codes, r.scale, r.zero)
+            if key is not None:
+                self.__dict__["_int_w_cache"] = hit
+            else:
+                self.__dict__.pop("_int_w_cache", None)
+        return intmm.int_linear(x2d, hit[1], hit[2], hit[3], x2d.shape[1], bits=self.quant.num_bits, min_dev=rng[0],
+                                max_dev=rng[1], bias=qbias)
+
+    def _int_conv1x1(self, input, weight, bias, qbias):
+        x = input[:, :, ::self.stride[0], ::self.stride[1]]
+        n, c, h, w = x.shape
+        x2d = x.permute(0, 2, 3, 1).contiguous().view(n * h * w, c)   # channels last: a row per pixel
+        y = self._int_product(x2d, weight, bias, qbias)
+        return y.view(n, h, w, -1).permute(0, 3, 1, 2).contiguous()
+
+    def _int_linear(self, input, weight, bias, qbias):
+        x2d = input.reshape(-1, input.shape[-1]).contiguous()
+        return self._int_product(x2d, weight, bias, qbias).view(*input.shape[:-1], -1)
+
     def _qparams(self, weight, bias):
         # a layer quantize_targ_layer left in an MX format (weight_format="mxfp4" / "mxfp8") holds
         # its block-scaled values already: a per-tensor integer grid would move them
@@ -541,6 +619,8 @@ class QuantConv2d(_QuantWeightMixin, nn.Conv2d):
         fmt = self._mx_format()
         if fmt is not None:
             return self._mx_conv(input, self.weight, self.bias, qweight, qbias, fmt)
+        if self._int_routed():
+            return self._int_conv1x1(input, self.weight, self.bias, qbias)
         return F.conv2d(input, qweight, qbias, self.stride, self.padding, self.dilation, self.groups)
 
 
@@ -573,6 +653,8 @@ class QuantLinear(_QuantWeightMixin, nn.Linear):
         fmt = self._mx_format()
         if fmt is not None:
             return self._mx_linear(input, self.weight, self.bias, qweight, qbias, fmt)
+        if self._int_routed():
+            return self._int_linear(input, self.weight, self.bias, qbias)
         return F.linear(input, qweight, qbias)
 
 
@@ -628,6 +710,8 @@ class QConv2d(QuantConv2d):
         fmt = self._mx_format()
         if fmt is not None:
             return self._mx_conv(input, w, b, qweight, qbias, fmt)
+        if self._int_routed():
+            return self._int_conv1x1(input, w, b, qbias)
         return F.conv2d(input, qweight, qbias, self.stride, self.padding, self.dilation, self.groups)
 
 
@@ -668,6 +752,8 @@ class QLinear(QuantLinear):
         fmt = self._mx_format()
         if fmt is not None:
             return self._mx_linear(input, w, b, qweight, qbias, fmt)
+        if self._int_routed():
+            return self._int_linear(input, w, b, qbias)
         return F.linear(input, qweight, qbias)
 
 

@@ -651,6 +651,103 @@ typedef struct dfq_mx_conv2d_desc {
 } dfq_mx_conv2d_desc;
 int dfq_mx_conv2d(const dfq_mx_conv2d_desc* d, void* stream);
 
+/* ---- integer matrix multiply on the i8 matrix instruction (no reference counterpart) ----
+ * out[m][n] = sum_k A[m][k] * B[n][k] (+ bias[n]) of the affine values the sweep's integer
+ * codes stand for,
+ *   A[m][k] = qa[m][k] * sa + za            (per tensor),
+ *   B[n][k] = qb[n][k] * sb[n] + zb[n]      (per tensor, or per row with DFQ_INT_B_PER_ROW),
+ * with qa, qb the code bytes read as full 8-bit integers (uint8 when *_signed is 0, int8 when
+ * 1; so every 2..8-bit grid in a byte container works and there is no bits field), or, for
+ * B with DFQ_INT_B_PACK4, the sweep's DFQ_PACK_INT4 nibbles (element 2k in the low nibble,
+ * two's-complement nibbles when b_signed).  Both operands are K-contiguous: a_codes [M, K]
+ * bytes, b_codes [N, K] bytes or [N, K / 2] packed bytes (K even, so every row starts on a
+ * byte).  The products run on v_mfma_i32_16x16x64_i8 (signed x signed: unsigned bytes are
+ * moved to the signed domain by xor 0x80 and the offset is folded back in integers), the row
+ * sums on the same instruction against an all-ones operand; no dequantized operand exists.
+ * Numerics: with the exact integers
+ *   P = sum_k qa * qb,   Sa[m] = sum_k qa,   Sb[n] = sum_k qb
+ * (each inside int32 because K <= 32768: 255 * 255 * 32768 < 2^31) the result is
+ *   acc  = ((double)sa * (double)sb[n]) * (double)P
+ *   acc += ((double)sa * (double)zb[n]) * (double)Sa[m]      -- if b_zero
+ *   acc += ((double)za * (double)sb[n]) * (double)Sb[n]      -- if a_zero
+ *   acc += ((double)za * (double)zb[n]) * (double)K          -- if both
+ *   acc += (double)bias[n]                                   -- if bias
+ *   out  = (float)acc
+ * in fp64, one IEEE operation per step in this order, no contraction (the float x float
+ * products are exact in double): the real-number product of the affine values to within
+ * fp64 rounding, rounded once to fp32, and bit for bit what numpy float64 gives.  A NULL
+ * zero skips its terms.  An element is one accumulator of one lane, the K steps (64
+ * elements) in order, no split of K, no atomics, no workspace: the same bits from run to
+ * run, whatever ldo, the addresses or the load path (K % 16 == 0 takes 16-B loads, 8-B for
+ * packed B; any other K takes byte loads with the same results).
+ * Asynchronous on `stream`, no host wait.  Checked on the host before any device call:
+ * DFQ_ERR_INVALID for a NULL a_codes, a_scale, b_codes, b_scale or out, M, N or K < 1 (M or
+ * N above 2^40), a_signed or b_signed not 0 / 1, unknown flags, non-zero reserved, a code
+ * base not 16-B aligned, out, bias, a scale or a zero not 4-B aligned; DFQ_ERR_SHAPE for
+ * ldo < N; DFQ_ERR_UNSUPPORTED for K > 32768, packed B with an odd K, a grid beyond int32. */
+#define DFQ_INT_B_PACK4    0x1  /* b_codes holds packed nibbles (DFQ_PACK_INT4's layout) */
+#define DFQ_INT_B_PER_ROW  0x2  /* b_scale / b_zero hold N values (per output channel), else 1 */
+#define DFQ_INT_MAX_K      32768  /* the largest K: 255 * 255 * 32768 < 2^31 */
+typedef struct dfq_int_gemm_desc {
+    const void*  a_codes;   /* [M, K] bytes */
+    const float* a_scale;   /* device, 1 value */
+    const float* a_zero;    /* device, 1 value, or NULL (0) */
+    const void*  b_codes;   /* [N, K] bytes, or [N, K / 2] with DFQ_INT_B_PACK4 */
+    const float* b_scale;   /* device, 1 or N values */
+    const float* b_zero;    /* device, 1 or N values, or NULL (0) */
+    const float* bias;      /* [N] or NULL */
+    float*       out;       /* [M, N] fp32, row stride ldo */
+    int64_t      ldo;       /* >= N */
+    int64_t      M;
+    int64_t      N;
+    int64_t      K;         /* <= 32768 */
+    int32_t      a_signed;  /* 0: uint8 codes, 1: int8 codes */
+    int32_t      b_signed;
+    int32_t      flags;     /* DFQ_INT_B_PACK4 | DFQ_INT_B_PER_ROW */
+    int32_t      reserved;  /* 0 */
+} dfq_int_gemm_desc;
+int dfq_int_gemm(const dfq_int_gemm_desc* d, void* stream);
+
+/* ---- integer linear in one launch: dfq_int_gemm with the activation quantized in the kernel ----
+ * The same product with A given as fp32 x [M, K] (row stride ldx), quantized to x_bits
+ * (2..8) inside the kernel by dfq_fake_quant_given's quantizer: the range is, by priority,
+ * min_dev[0] / max_dev[0] (device floats read as exact doubles) or given_min / given_max;
+ * flags may hold DFQ_SCALE_F32 (0-d tensor bounds) next to dfq_int_gemm's; the parameters
+ * are make_qparams' and the code of an element is the q of
+ *   q = rint(clamp((x + negmn) / s, qmin, qmax)),
+ * uint8 when x_symmetric is 0 and int8 when 1, with sa = s and za = min (+0 when symmetric,
+ * always present).  Each lane quantizes the 16 elements its operand of the instruction
+ * stands for; the codes of x never reach memory.  The result is bit for bit what
+ * dfq_quantize_tensor (given range; codes, scale and zero of x) followed by dfq_int_gemm
+ * gives.  Elements at k >= K and rows >= M are never read.  x 16-B aligned with ldx % 4 == 0
+ * and K % 4 == 0 takes 16-B loads, every other case 4-B loads with the same results.
+ * Checks as dfq_int_gemm's, and DFQ_ERR_INVALID for a NULL x, x_bits outside 2..8,
+ * x_symmetric not 0 / 1, x, min_dev or max_dev not 4-B aligned; DFQ_ERR_SHAPE for ldx < K. */
+typedef struct dfq_int_linear_desc {
+    const float* x;         /* fp32 [M, K], K-contiguous, row stride ldx elements */
+    const float* min_dev;   /* device float or NULL: the range's min (else given_min) */
+    const float* max_dev;   /* device float or NULL: the range's max (else given_max) */
+    const void*  b_codes;   /* as dfq_int_gemm's */
+    const float* b_scale;
+    const float* b_zero;
+    const float* bias;
+    float*       out;
+    double       given_min;
+    double       given_max;
+    int64_t      ldx;       /* >= K */
+    int64_t      ldo;       /* >= N */
+    int64_t      M;
+    int64_t      N;
+    int64_t      K;
+    int32_t      x_bits;    /* 2..8 */
+    int32_t      x_symmetric;
+    int32_t      b_signed;
+    int32_t      flags;     /* DFQ_INT_B_PACK4 | DFQ_INT_B_PER_ROW | DFQ_SCALE_F32 */
+    int32_t      reserved;  /* 0 */
+    int32_t      reserved2; /* 0 */
+} dfq_int_linear_desc;
+int dfq_int_linear(const dfq_int_linear_desc* d, void* stream);
+
 /* ---- high-bias absorption (bias_absorption.py:147-197) ------------------
  * c = max(bn_b - N*bn_w, 0) (bn_* = the BN's fake_weight / fake_bias);
  * b2[o] += sum_i (sum_k W2[o,i,k]) * c[g*i2 + i];  b1 -= c;  bn_b -= c.
