@@ -40,7 +40,7 @@ EXPORTS = [
     "dfq_clip_search_ws_bytes", "dfq_clip_search_batch",
     "dfq_mx_quantize_ws_bytes", "dfq_mx_quantize_batch", "dfq_mx_quantize_search_batch", "dfq_mx_gemm",
     "dfq_mx_linear", "dfq_mx_conv2d",
-    "dfq_int_gemm", "dfq_int_linear",
+    "dfq_int_gemm", "dfq_int_linear", "dfq_int_conv2d",
 ]
 #: entry points only the diagnostics library exports (include/dfq_diag.h)
 DIAG_EXPORTS = ["dfq_probe_stream", "dfq_probe_lds", "dfq_debug_timeline", "dfq_debug_ablate",
@@ -167,6 +167,19 @@ class IntLinearDesc(C.Structure):
     ]
 
 
+class IntConv2dDesc(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("min_dev", C.c_void_p), ("max_dev", C.c_void_p), ("b_codes", C.c_void_p),
+        ("b_scale", C.c_void_p), ("b_zero", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p),
+        ("given_min", C.c_double), ("given_max", C.c_double),
+        ("B", C.c_int64), ("C", C.c_int64), ("H", C.c_int64), ("W", C.c_int64), ("N", C.c_int64), ("KH", C.c_int64),
+        ("KW", C.c_int64), ("stride_h", C.c_int64), ("stride_w", C.c_int64), ("pad_h", C.c_int64), ("pad_w", C.c_int64),
+        ("dil_h", C.c_int64), ("dil_w", C.c_int64),
+        ("x_bits", C.c_int32), ("x_symmetric", C.c_int32), ("b_signed", C.c_int32), ("flags", C.c_int32),
+        ("reserved", C.c_int32), ("reserved2", C.c_int32),
+    ]
+
+
 DFQ_BC_OP_EXPECT, DFQ_BC_OP_APPLY, DFQ_BC_OP_PROPAGATE, DFQ_BC_OP_COPY = 0, 1, 2, 3
 DFQ_BC_APPLY_VEC_SCRATCH = 1
 DFQ_BN_FOLD_ZERO_BIAS = 1
@@ -265,6 +278,7 @@ def load(path: Optional[os.PathLike] = None) -> C.CDLL:
         "dfq_mx_conv2d": ([C.POINTER(MxConv2dDesc), P], C.c_int),
         "dfq_int_gemm": ([C.POINTER(IntGemmDesc), P], C.c_int),
         "dfq_int_linear": ([C.POINTER(IntLinearDesc), P], C.c_int),
+        "dfq_int_conv2d": ([C.POINTER(IntConv2dDesc), P], C.c_int),
     }
     diag = {
         "dfq_probe_stream": ([P, P, P, P, I64, I32, P], C.c_int),

@@ -139,6 +139,50 @@ DFQ_HOST_DEVICE inline bool mxc_out_quad(const MxcGeom& g, int64_t m, int64_t M)
     return m + 3 < M && (uint32_t)m % (uint32_t)g.OHW + 3 < (uint32_t)g.OHW;
 }
 
+// The geometry checks of dfq_mx_conv2d and dfq_int_conv2d (no device call), whose descriptors
+// name the geometry alike.  mxc_check_extents: every extent, stride, dilation and padding at
+// least 1 (padding 0) and at most 2^28, so that H + 2 ph + dh (and W's) stays inside int32, and
+// the offsets inside one image of x and the im2col column inside int32 (factor by factor: no
+// product overflows).  mxc_check_geometry, after it: the output extents, M, K, the geometry as
+// the kernel takes it and the grid.
+template <class Desc>
+inline int mxc_check_extents(const Desc& d) {
+    constexpr int64_t kMax = int64_t(1) << 28;
+    const int64_t least_one[] = {d.B, d.C, d.H, d.W, d.N, d.KH, d.KW, d.stride_h, d.stride_w, d.dil_h, d.dil_w};
+    for (int64_t v : least_one)
+        if (v < 1 || v > kMax) return DFQ_ERR_INVALID;
+    const int64_t least_zero[] = {d.pad_h, d.pad_w};
+    for (int64_t v : least_zero)
+        if (v < 0 || v > kMax) return DFQ_ERR_INVALID;
+    constexpr int64_t k31 = int64_t(1) << 31;
+    if (d.H * d.W >= k31 || d.C * (d.H * d.W) >= k31) return DFQ_ERR_INVALID;
+    if (d.KH * d.KW >= k31 || d.C * (d.KH * d.KW) >= k31) return DFQ_ERR_INVALID;
+    return DFQ_OK;
+}
+template <class Desc>
+inline int mxc_check_geometry(const Desc& d, MxcGeom& g, int64_t& M, int64_t& K, int64_t& grid) {
+    constexpr int64_t k31 = int64_t(1) << 31;
+    const int64_t OH = mxc_out_extent(d.H, d.pad_h, d.dil_h, d.KH, d.stride_h);
+    const int64_t OW = mxc_out_extent(d.W, d.pad_w, d.dil_w, d.KW, d.stride_w);
+    if (OH < 1 || OW < 1) return DFQ_ERR_SHAPE;
+    if (OH * OW >= k31 || d.N * (OH * OW) >= k31) return DFQ_ERR_INVALID;   // offsets inside one image of out
+    if (d.B * (OH * OW) > k31) return DFQ_ERR_INVALID;                      // M, as dfq_mx_gemm's
+    K = d.C * d.KH * d.KW;
+    M = d.B * OH * OW;
+    if (d.N > (int64_t(1) << 50) / K) return DFQ_ERR_INVALID;               // B's code offsets
+    g.C = (int32_t)d.C; g.H = (int32_t)d.H; g.W = (int32_t)d.W; g.N = (int32_t)d.N;
+    g.KH = (int32_t)d.KH; g.KW = (int32_t)d.KW; g.OH = (int32_t)OH; g.OW = (int32_t)OW;
+    g.sh = (int32_t)d.stride_h; g.sw = (int32_t)d.stride_w; g.ph = (int32_t)d.pad_h; g.pw = (int32_t)d.pad_w;
+    g.dh = (int32_t)d.dil_h; g.dw = (int32_t)d.dil_w;
+    g.HW = g.H * g.W; g.OHW = g.OH * g.OW; g.KHW = g.KH * g.KW;
+    g.CHW = (int64_t)g.C * g.HW;
+    g.NOHW = (int64_t)g.N * g.OHW;
+    const int64_t n = mxg_grid(M, d.N);
+    if (n > 0x7fffffff) return DFQ_ERR_UNSUPPORTED;
+    grid = n;
+    return DFQ_OK;
+}
+
 // dfq_mx_conv2d's argument checks (no device call): DFQ_OK with the geometry, M, K and the
 // grid, or the error.
 int mxc_check(const dfq_mx_conv2d_desc* d, MxcGeom& g, int64_t& M, int64_t& K, int64_t& grid);

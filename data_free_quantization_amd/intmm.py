@@ -1,10 +1,12 @@
 """Integer matrix multiply on the i8 matrix instruction for the sweep's integer codes.
 
-Host wrappers of ``dfq_int_gemm`` and ``dfq_int_linear`` (include/dfq_hip.h):
-``int_gemm`` multiplies two operands given as the integer codes, scales and zeros the sweep
-(or ``utils.quantize.fake_quant``) writes -- uint8 / int8 bytes, or packed INT4 nibbles for
-B -- and ``int_linear`` multiplies an fp32 input, quantized inside the kernel by
-``fake_quant_given``'s quantizer, with such a B in one launch.  The integer sums are exact
+Host wrappers of ``dfq_int_gemm``, ``dfq_int_linear`` and ``dfq_int_conv2d`` (include/dfq_hip.h;
+DESIGN.md 3.9): ``int_gemm`` multiplies two operands given as the integer codes, scales and
+zeros the sweep (or ``utils.quantize.fake_quant``) writes -- uint8 / int8 bytes, or packed INT4
+nibbles for B -- ``int_linear`` multiplies an fp32 input, quantized inside the kernel by
+``fake_quant_given``'s quantizer, with such a B in one launch, and ``int_conv2d`` does that on
+the im2col rows of an NCHW input, gathered inside the kernel, with zero padding standing for
+the real value 0.  The integer sums are exact
 and the affine terms are applied in fp64 in a fixed order, so every output is bit for bit a
 numpy float64 statement (tests/int_gemm_cases.py).  There is no CPU fallback: CPU tensors
 raise."""
@@ -78,6 +80,20 @@ def _b_args(d, b_codes, b_scale, b_zero, K: int, b_packed: bool) -> int:
     return N
 
 
+def _range_args(d, min_dev, max_dev, min_value, max_value, scale_f32: bool) -> None:
+    """The quantizer's range: its checks and descriptor fields (int_linear's and int_conv2d's)."""
+    for name, dev_v, host_v in (("min", min_dev, min_value), ("max", max_dev, max_value)):
+        if dev_v is not None:
+            _param_arg(name + "_dev", dev_v, (1,))
+        elif host_v is None:
+            raise ValueError("the range's %s is missing: pass %s_dev or %s_value" % (name, name, name))
+    d.min_dev = min_dev.data_ptr() if min_dev is not None else None
+    d.max_dev = max_dev.data_ptr() if max_dev is not None else None
+    d.given_min = float(min_value) if min_value is not None else 0.0
+    d.given_max = float(max_value) if max_value is not None else 0.0
+    d.flags = _lib.DFQ_SCALE_F32 if scale_f32 else 0
+
+
 def _bias_out_args(what: str, d, M: int, N: int, K: int, dev, bias, out, others) -> torch.Tensor:
     """mx.py's checks of ``bias``, ``out`` and the tensors' device; the descriptor fields both entries share."""
     out = mx._bias_out_args(what, M, N, dev, bias, out, others)
@@ -147,21 +163,74 @@ def int_linear(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor, b_
         raise ValueError("x must be [M, %d] with unit column stride and a row stride >= %d, got %s with strides %s"
                          % (K, K, tuple(x.shape), tuple(x.stride())))
     d = _lib.IntLinearDesc()
-    for name, dev_v, host_v in (("min", min_dev, min_value), ("max", max_dev, max_value)):
-        if dev_v is not None:
-            _param_arg(name + "_dev", dev_v, (1,))
-        elif host_v is None:
-            raise ValueError("the range's %s is missing: pass %s_dev or %s_value" % (name, name, name))
-    d.min_dev = min_dev.data_ptr() if min_dev is not None else None
-    d.max_dev = max_dev.data_ptr() if max_dev is not None else None
-    d.given_min = float(min_value) if min_value is not None else 0.0
-    d.given_max = float(max_value) if max_value is not None else 0.0
-    d.flags = _lib.DFQ_SCALE_F32 if scale_f32 else 0
+    _range_args(d, min_dev, max_dev, min_value, max_value, scale_f32)
     N = _b_args(d, b_codes, b_scale, b_zero, K, bool(b_packed))
     M, dev = x.shape[0], x.device
     out = _bias_out_args("int_linear", d, M, N, K, dev, bias, out, (min_dev, max_dev, b_codes, b_scale, b_zero))
     d.x, d.ldx = x.data_ptr(), (x.stride(0) if M > 1 else max(x.stride(0), K))
     d.x_bits, d.x_symmetric = bits, int(bool(symmetric))
     _lib.check(_lib.load().dfq_int_linear(C.byref(d), _lib.raw_stream(dev)), "dfq_int_linear", ValueError)
+    LINEAR_CALLS += 1
+    return out
+
+
+def int_conv2d(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor, b_zero: Optional[torch.Tensor], kernel_size,
+               stride=1, padding=0, dilation=1, *, bits: int = 8, symmetric: bool = False,
+               min_dev: Optional[torch.Tensor] = None, max_dev: Optional[torch.Tensor] = None, min_value=None,
+               max_value=None, scale_f32: bool = False, b_packed: bool = False, bias: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The convolution (groups == 1, zero padding) of the affine values the codes stand for, in
+    one launch (dfq_int_conv2d): ``x`` fp32 contiguous NCHW [B, C, H, W], read in
+    place and quantized to ``bits`` inside the kernel as ``int_linear`` quantizes its input; B the
+    weight [N, C, KH, KW] as codes with rows of K = C * KH * KW elements along (c, kh, kw) --
+    ``fake_quant(weight.reshape(N, -1))``'s -- with ``b_scale`` / ``b_zero`` / ``b_packed`` as for
+    ``int_gemm``.  A padding tap has the real value 0, as in ``F.conv2d`` of the fake-quantized
+    input: it is absent from every sum, not the code of 0.0 (which ``int_linear`` on ``F.unfold``'s
+    matrix would use).  Where the geometry has no padding the result is bit for bit ``int_linear``
+    on that matrix, reshaped to NCHW.  ``kernel_size``, ``stride``, ``padding``, ``dilation``: ints
+    or (h, w) pairs.  ``out``: fp32 contiguous [B, N, OH, OW]; allocated when None.  Counts in
+    ``LINEAR_CALLS``.  Asynchronous on the current stream."""
+    global LINEAR_CALLS
+    bits = int(bits)
+    if not 2 <= bits <= 8:
+        raise ValueError("bits must be 2..8, got %d" % bits)
+    _on_gpu("x", x, "a float32 tensor")
+    if x.dtype != torch.float32:
+        raise TypeError("x: float32 on the GPU")
+    (KH, KW), (sh, sw) = mx._pair(kernel_size, "kernel_size"), mx._pair(stride, "stride")
+    (ph, pw), (dh, dw) = mx._pair(padding, "padding"), mx._pair(dilation, "dilation")
+    if min(KH, KW, sh, sw, dh, dw) < 1 or min(ph, pw) < 0:
+        raise ValueError("kernel_size, stride and dilation must be >= 1 and padding >= 0")
+    if x.dim() != 4 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError("x must be a contiguous [B, C, H, W] tensor, got %s with strides %s" % (tuple(x.shape), tuple(x.stride())))
+    B, Cin, H, W = x.shape
+    K = _k_arg(Cin * KH * KW)
+    d = _lib.IntConv2dDesc()
+    _range_args(d, min_dev, max_dev, min_value, max_value, scale_f32)
+    N = _b_args(d, b_codes, b_scale, b_zero, K, bool(b_packed))
+    OH, OW = mx.conv_out_size(H, KH, sh, ph, dh), mx.conv_out_size(W, KW, sw, pw, dw)
+    if OH < 1 or OW < 1:
+        raise ValueError("the kernel %s (dilation %s) does not fit the padded input %s" % ((KH, KW), (dh, dw), (H + 2 * ph, W + 2 * pw)))
+    dev = x.device
+    if bias is not None:
+        _lib.require_device(bias)
+        if bias.numel() != N:
+            raise ValueError("bias holds %d elements, %d needed" % (bias.numel(), N))
+    if out is None:
+        out = torch.empty((B, N, OH, OW), dtype=torch.float32, device=dev)
+    else:
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32:
+            raise TypeError("out: float32 on the GPU")
+        if tuple(out.shape) != (B, N, OH, OW) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous [%d, %d, %d, %d] tensor" % (B, N, OH, OW))
+    for t in (min_dev, max_dev, b_codes, b_scale, b_zero, bias, out):
+        if t is not None and t.device != dev:
+            raise ValueError("every tensor of an int_conv2d call must live on one device")
+    d.x, d.out = x.data_ptr(), out.data_ptr()
+    d.bias = bias.data_ptr() if bias is not None else None
+    d.B, d.C, d.H, d.W, d.N, d.KH, d.KW = B, Cin, H, W, N, KH, KW
+    d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w = sh, sw, ph, pw, dh, dw
+    d.x_bits, d.x_symmetric = bits, int(bool(symmetric))
+    _lib.check(_lib.load().dfq_int_conv2d(C.byref(d), _lib.raw_stream(dev)), "dfq_int_conv2d", ValueError)
     LINEAR_CALLS += 1
     return out

@@ -64,6 +64,12 @@ Same flags and stage order; the transforms run on the GPU.  Additive flags:
                        deployment of the quantized model computes, integer sums exact, the
                        affine terms in fp64.  k x k, grouped and depthwise convolutions stay on
                        fp32.  Needs --quantize and --weight_format int; not with --mx_matmul
+  --int_matmul_conv    with --int_matmul: every convolution with groups == 1 and zero padding mode
+                       -- any kernel size, stride, padding and dilation -- multiplies on the i8
+                       matrix instruction too (intmm.int_conv2d, dfq_int_conv2d): one launch
+                       gathers the im2col rows from the NCHW input, quantizes them and stores
+                       NCHW; a padding tap is the real value 0, as in F.conv2d.  Grouped and
+                       depthwise convolutions stay on fp32.  Needs --int_matmul
 
 Example (README.md:137 of the reference):
   python -m data_free_quantization_amd.main_dfq --task cls --relu --equalize --absorption \
@@ -144,6 +150,9 @@ def get_argument(argv=None):
     p.add_argument("--int_matmul", action="store_true",
                    help="evaluate with the integer layers' Linear and 1x1-convolution products on the i8 matrix "
                         "instruction, from the weight and activation codes")
+    p.add_argument("--int_matmul_conv", action="store_true",
+                   help="with --int_matmul: k x k convolutions (groups == 1) multiply on the i8 matrix instruction too, "
+                        "their im2col rows gathered and quantized inside the kernel")
     p.add_argument("--mx_scale_search", action="store_true",
                    help="MX weights: per block, the better of the floor rule's scale and the next one up by "
                         "the block's own quantization noise")
@@ -154,6 +163,8 @@ def get_argument(argv=None):
         p.error("--mx_matmul_fused needs --mx_matmul")
     if args.mx_matmul_conv and args.mx_matmul is None:
         p.error("--mx_matmul_conv needs --mx_matmul")
+    if args.int_matmul_conv and not args.int_matmul:
+        p.error("--int_matmul_conv needs --int_matmul")
     if args.int_matmul and args.mx_matmul is not None:
         p.error("--int_matmul conflicts with --mx_matmul")
     if args.int_matmul and (not args.quantize or args.weight_format != "int"):
@@ -368,7 +379,7 @@ def main(argv=None):
         import contextlib
         from .utils.quantize import frozen_weights, int_matmul_forward, mx_matmul_forward
         scope = (mx_matmul_forward(args.mx_matmul, fused=args.mx_matmul_fused, conv=args.mx_matmul_conv) if args.mx_matmul is not None
-                 else int_matmul_forward() if args.int_matmul else contextlib.nullcontext())
+                 else int_matmul_forward(conv=args.int_matmul_conv) if args.int_matmul else contextlib.nullcontext())
         with frozen_weights(), scope:
             accuracy = inference_all(model, args.task, args)
         print(f"Inference time is {time.time() - start} seconds")

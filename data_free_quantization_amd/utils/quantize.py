@@ -408,10 +408,11 @@ def mx_matmul_forward(act_format: str = "mxfp8", fused: bool = False, conv: bool
 
 
 _INT_MATMUL = False   # an int_matmul_forward() scope is open
+_INT_CONV = False     # that scope's convolutions multiply through intmm.int_conv2d
 
 
 @contextlib.contextmanager
-def int_matmul_forward():
+def int_matmul_forward(conv: bool = False):
     """Inference with the integer layers' products on the i8 matrix instruction: inside this
     scope a Quant* layer whose ``weight_format`` mark is "int" (the default) multiplies through
     ``intmm.int_linear`` -- its weight's integer codes times its input's activation codes --
@@ -428,15 +429,24 @@ def int_matmul_forward():
     bits; beyond it a code may move by one.  The bias fake quant stays and is
     added in the kernel.  k x k, grouped and depthwise convolutions, MX layers and everything
     outside the scope are untouched.  The scope resets ``intmm.LINEAR_CALLS``.  An inference
-    path: under autograd the layers raise."""
+    path: under autograd the layers raise.
+    ``conv``: every QuantConv2d / QConv2d with groups == 1, padding_mode "zeros", an int or tuple
+    padding and C * KH * KW <= ``intmm.MAX_K`` -- any kernel size, stride and dilation, the 1x1
+    layers included -- multiplies through ``intmm.int_conv2d`` (``dfq_int_conv2d``) on its NCHW
+    input as it is: one launch gathers the im2col rows, quantizes them and stores NCHW, and a
+    padding tap is the real value 0, as in ``F.conv2d`` of the fake-quantized input.  The weight
+    codes, the range and the bias are the same; each call counts in ``intmm.LINEAR_CALLS``.  An
+    unpadded 1x1 layer gives the bits it gives with ``conv=False``.  Grouped and depthwise
+    convolutions, string padding and other padding modes stay on ``F.conv2d``.  The scope nests
+    and restores like ``mx_matmul_forward``'s."""
     from .. import intmm
-    global _INT_MATMUL
-    prev, _INT_MATMUL = _INT_MATMUL, True
+    global _INT_MATMUL, _INT_CONV
+    prev, _INT_MATMUL, _INT_CONV = (_INT_MATMUL, _INT_CONV), True, bool(conv)
     intmm.reset_linear_calls()
     try:
         yield
     finally:
-        _INT_MATMUL = prev
+        _INT_MATMUL, _INT_CONV = prev
 
 
 class _QuantWeightMixin:
@@ -522,22 +532,28 @@ class _QuantWeightMixin:
         return self._mx_product(x2d, weight, bias, qweight, qbias, fmt).view(*input.shape[:-1], -1)
 
     def _int_routed(self):
-        """The layer's product runs through intmm.int_linear (int_matmul_forward)."""
+        """The layer's product runs through intmm.int_linear or intmm.int_conv2d (int_matmul_forward)."""
         if not _INT_MATMUL or self.__dict__.get("weight_format", "int") != "int":
             return False
         if self.num_bits > 8 or self.quant.num_bits > 8:
             return False
         if isinstance(self, nn.Conv2d):
-            return (tuple(self.kernel_size) == (1, 1) and self.groups == 1 and not isinstance(self.padding, str) and
-                    tuple(self.padding) == (0, 0))
+            return self._int_conv_routed() or (
+                tuple(self.kernel_size) == (1, 1) and self.groups == 1 and not isinstance(self.padding, str) and
+                tuple(self.padding) == (0, 0))
         return True
 
-    def _int_product(self, x2d, weight, bias, qbias):
-        """intmm.int_linear of the fake-quantized [rows, K] input with the weight's integer codes
-        (kept in frozen_weights()), on the range the observer just quantized the input with."""
+    def _int_conv_routed(self):
+        """The routed convolution multiplies through intmm.int_conv2d (int_matmul_forward(conv=True))."""
         from .. import intmm
+        return (_INT_CONV and self.groups == 1 and self.padding_mode == "zeros" and not isinstance(self.padding, str) and
+                self.in_channels * self.kernel_size[0] * self.kernel_size[1] <= intmm.MAX_K)
+
+    def _int_operands(self, x, weight, bias):
+        """The range the observer just quantized the input with, and the weight's integer codes,
+        scale and zero (kept in frozen_weights())."""
         rng = self.quant.__dict__.get("_given_range")
-        if rng is None or not _no_autograd(x2d, weight, bias):
+        if rng is None or not _no_autograd(x, weight, bias):
             raise RuntimeError("int_matmul_forward is an inference path: run it under torch.no_grad()")
         key = self._weight_key(weight, bias)
         hit = self.__dict__.get("_int_w_cache") if key is not None else None
@@ -549,8 +565,23 @@ class _QuantWeightMixin:
                 self.__dict__["_int_w_cache"] = hit
             else:
                 self.__dict__.pop("_int_w_cache", None)
-        return intmm.int_linear(x2d, hit[1], hit[2], hit[3], x2d.shape[1], bits=self.quant.num_bits, min_dev=rng[0],
-                                max_dev=rng[1], bias=qbias)
+        return rng, hit[1:]
+
+    def _int_product(self, x2d, weight, bias, qbias):
+        """intmm.int_linear of the fake-quantized [rows, K] input with the weight's integer codes,
+        on the range the observer just quantized the input with."""
+        from .. import intmm
+        rng, wq = self._int_operands(x2d, weight, bias)
+        return intmm.int_linear(x2d, *wq, x2d.shape[1], bits=self.quant.num_bits, min_dev=rng[0], max_dev=rng[1], bias=qbias)
+
+    def _int_conv(self, input, weight, bias, qbias):
+        """The layer's product: intmm.int_conv2d on the NCHW input (conv=True) or the 1x1 path."""
+        from .. import intmm
+        if not self._int_conv_routed():
+            return self._int_conv1x1(input, weight, bias, qbias)
+        rng, wq = self._int_operands(input, weight, bias)
+        return intmm.int_conv2d(input.detach().contiguous(), *wq, self.kernel_size, self.stride, self.padding, self.dilation,
+                                bits=self.quant.num_bits, min_dev=rng[0], max_dev=rng[1], bias=qbias)
 
     def _int_conv1x1(self, input, weight, bias, qbias):
         x = input[:, :, ::self.stride[0], ::self.stride[1]]
@@ -620,7 +651,7 @@ class QuantConv2d(_QuantWeightMixin, nn.Conv2d):
         if fmt is not None:
             return self._mx_conv(input, self.weight, self.bias, qweight, qbias, fmt)
         if self._int_routed():
-            return self._int_conv1x1(input, self.weight, self.bias, qbias)
+            return self._int_conv(input, self.weight, self.bias, qbias)
         return F.conv2d(input, qweight, qbias, self.stride, self.padding, self.dilation, self.groups)
 
 
@@ -711,7 +742,7 @@ class QConv2d(QuantConv2d):
         if fmt is not None:
             return self._mx_conv(input, w, b, qweight, qbias, fmt)
         if self._int_routed():
-            return self._int_conv1x1(input, w, b, qbias)
+            return self._int_conv(input, w, b, qbias)
         return F.conv2d(input, qweight, qbias, self.stride, self.padding, self.dilation, self.groups)
 
 

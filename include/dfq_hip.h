@@ -748,6 +748,83 @@ typedef struct dfq_int_linear_desc {
 } dfq_int_linear_desc;
 int dfq_int_linear(const dfq_int_linear_desc* d, void* stream);
 
+/* ---- integer convolution in one launch: dfq_int_linear on the im2col rows, gathered in the kernel ----
+ * The convolution of the affine values that the codes of x and of the weight stand for, with
+ * zero padding: a padding tap has the real value 0 -- its term is absent -- and is NOT the code
+ * the quantizer gives 0.0, which on an asymmetric range stands for q0 * s + min != 0.  (F.conv2d
+ * of the fake-quantized input pads with a real 0; quantizing the materialised F.unfold matrix
+ * does not.)  With
+ *   m = (b * OH + oh) * OW + ow,  k = (c * KH + i) * KW + j,  M = B * OH * OW,  K = C * KH * KW,
+ *   v[m][k] = 1 where x[b][c][oh * stride_h - pad_h + i * dil_h][ow * stride_w - pad_w + j * dil_w]
+ *             lies inside the image, else 0,
+ *   OH = (H + 2 pad_h - dil_h (KH - 1) - 1) / stride_h + 1  (OW alike),
+ * qa[m][k] the code dfq_fake_quant_given's quantizer gives x at that tap (dfq_int_linear's: the
+ * range from min_dev / max_dev or given_min / given_max, x_bits 2..8, sa = s, za = min, +0 when
+ * symmetric, always present) and qb [N, K] the weight's codes, rows along (c, kh, kw) -- the order
+ * [N, C, KH, KW] is stored in -- as dfq_int_gemm's B (bytes, or nibbles with DFQ_INT_B_PACK4), the
+ * exact integers
+ *   P[m][n]  = sum_k v qa qb     Sa[m] = sum_k v qa
+ *   Sb[m][n] = sum_k v qb        T[m]  = sum_k v
+ * (each inside int32 because K <= DFQ_INT_MAX_K) give
+ *   acc  = ((double)sa * (double)sb[n]) * (double)P[m][n]
+ *   acc += ((double)sa * (double)zb[n]) * (double)Sa[m]       -- if b_zero
+ *   acc += ((double)za * (double)sb[n]) * (double)Sb[m][n]
+ *   acc += ((double)za * (double)zb[n]) * (double)T[m]        -- if b_zero
+ *   acc += (double)bias[n]                                    -- if bias
+ *   out[b][n][oh][ow] = (float)acc
+ * in fp64, one IEEE operation per step in this order, no contraction.  So the result is bit for
+ * bit a numpy float64 statement; where no tap of the geometry falls in padding it is bit for
+ * bit dfq_int_linear on the materialised F.unfold matrix [M, K]; and a row wholly in padding
+ * stores (float)bias[n] (0 without a bias).  x is read in place, NCHW: a lane gathers the 16
+ * consecutive k of its operand with 4-B loads (the run's first tap decomposed once per K step,
+ * then walked kw -> kh -> c with carries) and quantizes them; padding taps and k >= K enter the
+ * instruction as 0 in its signed domain.  With padding, sum_k v qb depends on the row: the
+ * kernel multiplies a 0 / 1 mask operand with B's fragments on the same instruction (ten
+ * instructions a K step instead of eight), and T is a closed form of the row's position.  One
+ * accumulator per output element, the K steps (64 elements) in order, no split of K, no
+ * atomics, no workspace, no LDS: the same bits from run to run.  The result goes straight to
+ * NCHW, one 16-B store where a lane's four rows lie in one image.
+ * Asynchronous on `stream`, no host wait.  Checked on the host before any device call:
+ * DFQ_ERR_INVALID for a NULL x, b_codes, b_scale or out, unknown flags, non-zero reserved or
+ * reserved2, b_signed or x_symmetric not 0 / 1, x_bits outside 2..8, an extent (B, C, H, W, N,
+ * KH, KW), stride or dilation < 1, a padding < 0, any of these above 2^28, C * H * W,
+ * N * OH * OW or K at or above 2^31, M above 2^31, N * K above 2^50, x, out, bias, min_dev,
+ * max_dev, b_scale or b_zero not 4-B aligned, b_codes not 16-B aligned; DFQ_ERR_SHAPE when OH
+ * or OW comes out < 1; DFQ_ERR_UNSUPPORTED for K > DFQ_INT_MAX_K, packed B with an odd K, a
+ * grid beyond int32. */
+typedef struct dfq_int_conv2d_desc {
+    const float* x;         /* fp32 [B, C, H, W], contiguous; 4-B aligned */
+    const float* min_dev;   /* device float or NULL: the range's min (else given_min) */
+    const float* max_dev;   /* device float or NULL: the range's max (else given_max) */
+    const void*  b_codes;   /* [N, K] bytes, or [N, K / 2] with DFQ_INT_B_PACK4; K = C * KH * KW */
+    const float* b_scale;   /* device, 1 or N values */
+    const float* b_zero;    /* device, 1 or N values, or NULL (0) */
+    const float* bias;      /* [N] or NULL */
+    float*       out;       /* fp32 [B, N, OH, OW], contiguous */
+    double       given_min;
+    double       given_max;
+    int64_t      B;
+    int64_t      C;
+    int64_t      H;
+    int64_t      W;
+    int64_t      N;
+    int64_t      KH;
+    int64_t      KW;
+    int64_t      stride_h;
+    int64_t      stride_w;
+    int64_t      pad_h;
+    int64_t      pad_w;
+    int64_t      dil_h;
+    int64_t      dil_w;
+    int32_t      x_bits;    /* 2..8 */
+    int32_t      x_symmetric;
+    int32_t      b_signed;
+    int32_t      flags;     /* DFQ_INT_B_PACK4 | DFQ_INT_B_PER_ROW | DFQ_SCALE_F32 */
+    int32_t      reserved;  /* 0 */
+    int32_t      reserved2; /* 0 */
+} dfq_int_conv2d_desc;
+int dfq_int_conv2d(const dfq_int_conv2d_desc* d, void* stream);
+
 /* ---- high-bias absorption (bias_absorption.py:147-197) ------------------
  * c = max(bn_b - N*bn_w, 0) (bn_* = the BN's fake_weight / fake_bias);
  * b2[o] += sum_i (sum_k W2[o,i,k]) * c[g*i2 + i];  b1 -= c;  bn_b -= c.
