@@ -17,6 +17,9 @@ Outputs (all plain arrays, loadable with numpy allow_pickle=False):
                       (cases and inputs: tests/bc_edge_cases.py; section ``bc_edge``)
   act_edge_cases.npz  set_quant_minmax on tiny add / case (d.) models, per channel, ReLU6
                       and NaN included (tests/act_edge_cases.py; section ``act_edge``)
+  cle_edge_cases.npz  _layer_equalization, relation by relation, and the loop's metric for
+                      three iterations on the graphs of tests/cle_edge_cases.py (section
+                      ``cle_edge``)
   pipeline_<model>.npz  main_dfq stage order on the synthetic models of
                       data_free_quantization_amd.zoo (positional graph keys)
 The synthetic model weights come from zoo.init_synthetic (numpy PCG64), so the
@@ -676,6 +679,59 @@ def act_edge_cases():
     print("act edge cases:", len(AE.GRAPHS), "graphs,", len(flat), "distinct vectors")
 
 
+def cle_edge_cases():
+    """The reference's own _layer_equalization, relation by relation as its
+    cross_layer_equalization calls it (Cross_layer_equal.py:81-108), and its metric
+    expression (:107-108) at 8 torch threads, for exactly three iterations on every
+    graph and value set of tests/cle_edge_cases.py, unsigned and signed ->
+    cle_edge_cases.npz.  Per run ``<graph>.<values>.<u|s>``: ``.diffs`` (float64 [3]),
+    ``.small`` (every tensor of at most CE.ARRAY_MAX elements, concatenated in
+    CE.pack's order: weights, created or existing first-layer biases, BN fake
+    weight / bias, S) and ``.digests`` (h of each larger tensor, -0 folded); per
+    graph and value set ``.inputs``, the digest of its generated inputs."""
+    from tests import cle_edge_cases as CE
+    from tests.cle_replay import edge_graph, edge_state
+    torch.set_num_threads(CE.REF_THREADS)
+    A, t0 = {}, time.time()
+    for gname in CE.GRAPHS:
+        assert sum(len(c.layers) for c in CE.GRAPHS[gname]) <= CE.MAX_TARGET_LAYERS, gname
+        for vs in CE.VALUE_SETS:
+            A[f"{gname}.{vs}.inputs"] = np.array(CE.input_digest(gname, vs))
+            for signed in (False, True):
+                graph, rels = edge_graph(gname, vs, device="cpu", relation_cls=RefRelation)
+                diffs = []
+                with torch.no_grad():
+                    for _ in range(CE.ITERATIONS):
+                        old_graph = copy.deepcopy(graph)
+                        for rel in rels:
+                            first, second, bn_idx = rel.get_idxs()
+                            if graph[first].bias is None:   # :93-94
+                                graph[first].bias = nn.Parameter(
+                                    data=torch.zeros((graph[first].weight.size(0)), dtype=torch.float32),
+                                    requires_grad=False)
+                            graph[first].weight, graph[second].weight, graph[first].bias, S = \
+                                ref_cle._layer_equalization(graph[first].weight, graph[second].weight,
+                                                            graph[first].bias, graph[bn_idx].fake_weight,
+                                                            graph[bn_idx].fake_bias, s_min_max=list(CE.S_MIN_MAX),
+                                                            signed=signed, eps=0)
+                            rel.set_scale_vec(S)
+                        diff_list = [float(torch.mean(torch.abs(graph[k].weight - old_graph[k].weight)))
+                                     for k in graph if type(graph[k]) in TARG]
+                        diffs.append(float(np.sum(diff_list)))
+                W, B, BN, S = edge_state(graph, rels)
+                for d in (W, B):
+                    for a in d.values():
+                        assert a is None or np.isfinite(a).all(), (gname, vs, signed)
+                _, small, digests = CE.pack(gname, W, B, BN, S)
+                tag = f"{gname}.{vs}.{'s' if signed else 'u'}"
+                A[f"{tag}.diffs"] = np.array(diffs, dtype=np.float64)
+                A[f"{tag}.small"], A[f"{tag}.digests"] = small, digests
+        print(gname, f"{time.time() - t0:.1f} s")
+    np.savez_compressed(OUT / "cle_edge_cases.npz", **A)
+    print("cle edge cases:", len(CE.GRAPHS), "graphs x", len(CE.VALUE_SETS), "value sets x 2 range kinds,",
+          (OUT / "cle_edge_cases.npz").stat().st_size, "bytes")
+
+
 FWD_INPUT = {"mobilenetv2": (16, 3, 224, 224), "resnet50": (16, 3, 224, 224), "deeplab": (2, 3, 129, 129),
              "resnet18": (16, 3, 224, 224)}
 FWD_SEED = 2024
@@ -909,6 +965,8 @@ if __name__ == "__main__":
         bc_edge_cases()
     if "act_edge" in which:
         act_edge_cases()
+    if "cle_edge" in which:
+        cle_edge_cases()
     for m in ("mobilenetv2", "resnet50", "deeplab", "resnet18"):
         if m in which:
             pipeline(m, per_channel=(m == "mobilenetv2"))

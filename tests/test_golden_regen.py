@@ -7,7 +7,7 @@ Runs only in the development container, where the reference is importable
 (``/root/reference``, never on the GPU box): ``tests/golden/make_golden.py`` is run
 into a scratch directory (``DFQ_GOLDEN_OUT``) and every array is compared byte
 for byte with the committed file, ignoring ``stats`` (timings).  By default:
-``quant`` (+ the chunked ranges), ``transform``, ``bc_edge``, ``act_edge`` and a ResNet-18 pipeline through
+``quant`` (+ the chunked ranges), ``transform``, ``bc_edge``, ``act_edge``, ``cle_edge`` and a ResNet-18 pipeline through
 the per-channel block (a few seconds); ``DFQ_REGEN_ALL=1`` regenerates every
 committed ``pipeline_*.npz`` as well (~15 minutes on 8 cores; round 6 ran it:
 identical)."""
@@ -46,9 +46,9 @@ def _same(a_path, b_path, extra_ok=()):
 
 
 def test_unit_fixtures_regenerate_identically(tmp_path):
-    _regen(tmp_path, ["quant", "transform", "bc_edge", "act_edge"], 600)
+    _regen(tmp_path, ["quant", "transform", "bc_edge", "act_edge", "cle_edge"], 600)
     for name in ("quant_cases.npz", "chunk_cases.npz", "transform_cases.npz", "bc_edge_cases.npz",
-                 "act_edge_cases.npz"):
+                 "act_edge_cases.npz", "cle_edge_cases.npz"):
         _same(tmp_path / name, HERE / name)
 
 

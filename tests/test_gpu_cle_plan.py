@@ -13,29 +13,10 @@ import pytest
 import torch
 import torch.nn as nn
 
-from oracle import oracle as O
+from tests.cle_replay import _BN, _conv, _replay   # the module builders and the oracle's replay (shared)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-class _BN:
-    def __init__(self, c, rng, with_stats=True):
-        self.fake_weight = torch.from_numpy(rng.uniform(0.5, 1.5, c).astype(np.float32)).to(DEV) if with_stats \
-            else None
-        self.fake_bias = torch.from_numpy(rng.normal(0, 0.5, c).astype(np.float32)).to(DEV) if with_stats \
-            else None
-
-
-def _conv(o, i, k, groups=1, rng=None, bias=True, dead=None):
-    m = nn.Conv2d(i, o, k, groups=groups, bias=bias)
-    w = rng.normal(0, 1, m.weight.shape).astype(np.float32)
-    if dead is not None:
-        w[dead] = 0.0
-    m.weight.data = torch.from_numpy(w)
-    if bias:
-        m.bias.data = torch.from_numpy(rng.normal(0, 0.1, o).astype(np.float32))
-    return m.to(DEV)
 
 
 def _graph(seed, dead_dw=None):
@@ -66,36 +47,6 @@ def _graph(seed, dead_dw=None):
     rels = [Relation("a1", "a2", "a1bn"), Relation("b1", "b2", "b1bn"), Relation("a2", "a3", "a2bn"),
             Relation("c1", "c2", "c1bn"), Relation("b2", "b3", "b2bn")]
     return g, rels
-
-
-def _replay(g, rels, s_min_max, thr, count, signed, eps, max_iters=None):
-    """The reference loop with the oracle's _layer_equalization and metric
-    (max_iters: the device loop's iteration cap, which the reference has not)."""
-    tk = [k for k in g if type(g[k]) in (nn.Conv2d, nn.Linear)]
-    W = {k: g[k].weight.detach().cpu().numpy().copy() for k in tk}
-    B = {k: (g[k].bias.detach().cpu().numpy().copy() if g[k].bias is not None else None) for k in tk}
-    BN = {k: [None if v is None else v.cpu().numpy().copy() for v in (g[k].fake_weight, g[k].fake_bias)]
-          for k in g if isinstance(g[k], _BN)}
-    S = {}
-    diff, it_count, diffs = 1e8, 0, []
-    while diff > thr and it_count < count and (max_iters is None or len(diffs) < max_iters):
-        old = {k: W[k].copy() for k in tk}
-        for i, r in enumerate(rels):
-            a, b, bn = r.get_idxs()
-            if B[a] is None:
-                B[a] = np.zeros(W[a].shape[0], np.float32)
-            w1, w2, b1, fw, fb, s = O.cle_relation(W[a], W[b], B[a], BN[bn][0], BN[bn][1], s_min_max[0],
-                                                   s_min_max[1], signed, eps)
-            W[a], W[b], B[a], BN[bn] = w1, w2, b1, [fw, fb]
-            with np.errstate(over="ignore"):   # the dead channel: s = 1e8 every iteration
-                S[i] = s if i not in S else (S[i] * s).astype(np.float32)
-        dt = O.np_sum([O.mean_abs_diff(W[k], old[k]) for k in tk])
-        diffs.append(dt)
-        if abs(diff - dt) > 1e-9:
-            it_count, diff = 0, dt
-        else:
-            it_count += 1
-    return W, B, BN, S, diffs
 
 
 @pytest.mark.parametrize("signed,eps,smm,thr,count", [
