@@ -40,7 +40,7 @@ EXPORTS = [
     "dfq_clip_search_ws_bytes", "dfq_clip_search_batch",
     "dfq_mx_quantize_ws_bytes", "dfq_mx_quantize_batch", "dfq_mx_quantize_search_batch", "dfq_mx_gemm",
     "dfq_mx_linear", "dfq_mx_conv2d",
-    "dfq_int_gemm", "dfq_int_linear", "dfq_int_conv2d",
+    "dfq_int_gemm", "dfq_int_linear", "dfq_int_conv2d", "dfq_int_dwconv2d",
 ]
 #: entry points only the diagnostics library exports (include/dfq_diag.h)
 DIAG_EXPORTS = ["dfq_probe_stream", "dfq_probe_lds", "dfq_debug_timeline", "dfq_debug_ablate",
@@ -180,6 +180,10 @@ class IntConv2dDesc(C.Structure):
     ]
 
 
+class IntDwConv2dDesc(C.Structure):
+    _fields_ = [(("mult", t) if f == "N" else (f, t)) for f, t in IntConv2dDesc._fields_]   # N = C * mult
+
+
 DFQ_BC_OP_EXPECT, DFQ_BC_OP_APPLY, DFQ_BC_OP_PROPAGATE, DFQ_BC_OP_COPY = 0, 1, 2, 3
 DFQ_BC_APPLY_VEC_SCRATCH = 1
 DFQ_BN_FOLD_ZERO_BIAS = 1
@@ -190,6 +194,7 @@ DFQ_MX_FP4_E2M1, DFQ_MX_FP8_E4M3 = 0, 1
 DFQ_MX_FP6_E2M3, DFQ_MX_FP6_E3M2 = 0x23, 0x32   # self-describing (exponent, mantissa bits): 2 stays invalid
 DFQ_MX_TASK_ELEMS, DFQ_MX_ESUM_TASK_ELEMS = 4096, 2048
 DFQ_INT_B_PACK4, DFQ_INT_B_PER_ROW, DFQ_INT_MAX_K = 0x1, 0x2, 32768
+DFQ_INT_DW_MAX_TAPS, DFQ_INT_DW_TILE_H, DFQ_INT_DW_TILE_W, DFQ_INT_DW_LDS_BYTES = 64, 32, 64, 16384
 
 _LIB: Optional[C.CDLL] = None
 
@@ -279,6 +284,7 @@ def load(path: Optional[os.PathLike] = None) -> C.CDLL:
         "dfq_int_gemm": ([C.POINTER(IntGemmDesc), P], C.c_int),
         "dfq_int_linear": ([C.POINTER(IntLinearDesc), P], C.c_int),
         "dfq_int_conv2d": ([C.POINTER(IntConv2dDesc), P], C.c_int),
+        "dfq_int_dwconv2d": ([C.POINTER(IntDwConv2dDesc), P], C.c_int),
     }
     diag = {
         "dfq_probe_stream": ([P, P, P, P, I64, I32, P], C.c_int),

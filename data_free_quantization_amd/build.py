@@ -18,12 +18,13 @@ CSRC = PKG / "csrc"
 LIB = PKG / "libdfq_hip.so"
 # *.hip: device + host code for gfx950.  *.cpp: host-only code, compiled as plain
 # C++ (the sweep's, the graph transforms', the CLE loop's, the pair statistics', the clip search's, the MX pass's and
-# the MX matrix multiply's, the fused MX linear's, the MX convolution's, the integer matrix multiply's and the integer convolution's planners, which also build on their own for their sanitizer tests).
+# the MX matrix multiply's, the fused MX linear's, the MX convolution's, the integer matrix multiply's, the integer convolution's and the integer depthwise convolution's planners, which also build on their own for their sanitizer tests).
 SOURCES = ["dfq_lib.hip", "dfq_sweep.hip", "dfq_sweep_plan.cpp", "dfq_transform.hip", "dfq_bc.hip", "dfq_act.hip",
            "dfq_transform_plan.cpp", "dfq_cle.hip", "dfq_cle_relation.hip",
            "dfq_cle_plan.cpp", "dfq_stats.hip", "dfq_stats_plan.cpp", "dfq_clip.hip", "dfq_clip_plan.cpp", "dfq_mx.hip", "dfq_mx_plan.cpp",
            "dfq_mx_gemm.hip", "dfq_mx_gemm_plan.cpp", "dfq_mx_linear_plan.cpp", "dfq_mx_conv_plan.cpp",
-           "dfq_int_gemm.hip", "dfq_int_gemm_plan.cpp", "dfq_int_conv_plan.cpp"]
+           "dfq_int_gemm.hip", "dfq_int_gemm_plan.cpp", "dfq_int_conv_plan.cpp",
+           "dfq_int_dwconv.hip", "dfq_int_dwconv_plan.cpp"]
 # Diagnostics build (bench.py's ceiling probes, scripts/ A/B runs): the same
 # sources with -DDFQ_DIAGNOSTICS (the sweep's A/B variants and environment
 # switches) plus the probes (include/dfq_diag.h).  Never loaded by the product path.

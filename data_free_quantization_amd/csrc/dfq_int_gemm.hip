@@ -38,6 +38,7 @@
 
 #include "dfq_int_conv_plan.h"
 #include "dfq_int_gemm_plan.h"
+#include "dfq_int_quant.h"
 
 namespace dfq {
 namespace {
@@ -144,15 +145,6 @@ struct IgPackedB {
     }
 };
 
-struct IgAParams {
-    float s, z;
-    bool has_z;
-    uint32_t xm;   // ig_xor_mask of A's signedness
-    int off;       // ig_offset
-    QParams q;     // fp32 A only
-    float rs;      // fp32 A only: rcp(q.s), qdq_screen's
-};
-
 // Rows: the lane's rows of A, one per instruction tile of its wave tile, made once before the K
 // loop; at(i) is what fetch() takes for tile i and m(i) the row's index.  kMask: sum_k b' depends
 // on the row (a mask operand, mask()); taps(): the contract's T of an output row.
@@ -196,20 +188,9 @@ struct IgFp32A {
     static constexpr bool kMask = false;
     static __device__ __forceinline__ int64_t taps(const IgArgs& g, int64_t) { return g.K; }
     typedef float Fetched[kIgLaneK];
-    // the parameters as fq_given_kernel builds them
+    // the parameters as fq_given_kernel builds them (dfq_int_quant.h)
     static __device__ __forceinline__ IgAParams params(const IgArgs& g) {
-        double gmin = g.gmin, gmax = g.gmax;
-        if (g.min_dev) gmin = (double)((const DFQ_GLOBAL float*)g.min_dev)[0];
-        if (g.max_dev) gmax = (double)((const DFQ_GLOBAL float*)g.max_dev)[0];
-        IgAParams p;
-        p.q = make_qparams((float)gmin, (float)gmax, g.x_bits, g.x_symmetric != 0, g.x_flags | DFQ_GIVEN_RANGE, gmin, gmax);
-        p.rs = __builtin_amdgcn_rcpf(p.q.s);
-        p.s = p.q.s;
-        p.z = p.q.mn;
-        p.has_z = true;
-        p.xm = ig_xor_mask(g.x_symmetric != 0);
-        p.off = ig_offset(g.x_symmetric != 0);
-        return p;
+        return ig_quant_params(g.min_dev, g.max_dev, g.gmin, g.gmax, g.x_bits, g.x_symmetric, g.x_flags);
     }
     static __device__ __forceinline__ void fetch(Fetched& v, const IgArgs& g, int64_t row, int64_t step, int lane) {
         const DFQ_GLOBAL float* x = (const DFQ_GLOBAL float*)g.a;
@@ -228,28 +209,10 @@ struct IgFp32A {
             }
         }
     }
-    // qdq's q of elements 4 j .. 4 j + 3, four at a time as the sweep takes them: the screened
-    // reciprocal quotient, the IEEE divide only where a lane of the wave sits near a rounding
-    // boundary (qdq_screen; the same codes).  Every lane of a working wave gets here: the ballot
-    // is in wave-uniform control flow.  The word holds the bytes dfq_quantize_tensor stores.
+    // qdq's q of elements 4 j .. 4 j + 3 as a word of code bytes (ig_codes4: the screened quotient,
+    // the ballot in wave-uniform control flow -- every lane of a working wave gets here).
     static __device__ __forceinline__ uint32_t codes(const float (&x)[kIgLaneK], const IgAParams& p, int j) {
-        float t[4];
-        bool need[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) t[e] = qdq_screen(x[4 * j + e], p.q, p.rs, need[e]);
-        if (__builtin_amdgcn_ballot_w64(need[0] | need[1] | need[2] | need[3])) {   // wave-uniform, rare
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (need[e]) t[e] = qdq_exact_t(x[4 * j + e], p.q);
-        }
-        uint32_t w = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float q;
-            qdq_finish(t[e], p.q, q);
-            w |= ((uint32_t)(int)q & 0xFFu) << (8 * e);
-        }
-        return w;
+        return ig_codes4(&x[4 * j], p);
     }
     static __device__ __forceinline__ ig_v4i operand(const Fetched& x, const IgAParams& p, int nv) {
         ig_v4i v;

@@ -1,12 +1,13 @@
 """Integer matrix multiply on the i8 matrix instruction for the sweep's integer codes.
 
-Host wrappers of ``dfq_int_gemm``, ``dfq_int_linear`` and ``dfq_int_conv2d`` (include/dfq_hip.h;
+Host wrappers of ``dfq_int_gemm``, ``dfq_int_linear``, ``dfq_int_conv2d`` and ``dfq_int_dwconv2d`` (include/dfq_hip.h;
 DESIGN.md 3.9): ``int_gemm`` multiplies two operands given as the integer codes, scales and
 zeros the sweep (or ``utils.quantize.fake_quant``) writes -- uint8 / int8 bytes, or packed INT4
 nibbles for B -- ``int_linear`` multiplies an fp32 input, quantized inside the kernel by
 ``fake_quant_given``'s quantizer, with such a B in one launch, and ``int_conv2d`` does that on
 the im2col rows of an NCHW input, gathered inside the kernel, with zero padding standing for
-the real value 0.  The integer sums are exact
+the real value 0; ``int_dwconv2d`` is the depthwise convolution (groups == C) on the packed
+8-bit dot instruction, each input element quantized once.  The integer sums are exact
 and the affine terms are applied in fp64 in a fixed order, so every output is bit for bit a
 numpy float64 statement (tests/int_gemm_cases.py).  There is no CPU fallback: CPU tensors
 raise."""
@@ -20,6 +21,7 @@ import torch
 from . import _lib, mx
 
 MAX_K = _lib.DFQ_INT_MAX_K
+DW_MAX_TAPS = _lib.DFQ_INT_DW_MAX_TAPS
 _CODE_DTYPES = (torch.uint8, torch.int8)
 
 
@@ -232,5 +234,72 @@ def int_conv2d(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor, b_
     d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w = sh, sw, ph, pw, dh, dw
     d.x_bits, d.x_symmetric = bits, int(bool(symmetric))
     _lib.check(_lib.load().dfq_int_conv2d(C.byref(d), _lib.raw_stream(dev)), "dfq_int_conv2d", ValueError)
+    LINEAR_CALLS += 1
+    return out
+
+
+def int_dwconv2d(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor, b_zero: Optional[torch.Tensor], kernel_size,
+                 stride=1, padding=0, dilation=1, *, bits: int = 8, symmetric: bool = False,
+                 min_dev: Optional[torch.Tensor] = None, max_dev: Optional[torch.Tensor] = None, min_value=None,
+                 max_value=None, scale_f32: bool = False, b_packed: bool = False, bias: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The depthwise convolution (groups == C, zero padding) of the affine values the codes stand
+    for, in one launch on the packed 8-bit dot instruction (dfq_int_dwconv2d):
+    ``x`` fp32 contiguous NCHW [B, C, H, W], read in place, every element quantized once to
+    ``bits`` inside the kernel as ``int_linear`` quantizes its input; B the weight [N, 1, KH, KW] as
+    codes with rows of K = KH * KW elements -- ``fake_quant(weight.reshape(N, -1))``'s -- N a
+    multiple of C (output channel n reads input channel n // (N // C)), with ``b_scale`` /
+    ``b_zero`` / ``b_packed`` as for ``int_gemm`` (packed needs an even K: a 3 x 3 kernel is
+    refused).  K is at most ``DW_MAX_TAPS``.  A padding tap has the real value 0, as in
+    ``int_conv2d``, and every channel's result is bit for bit ``int_conv2d`` on that channel alone.
+    ``kernel_size``, ``stride``, ``padding``, ``dilation``: ints or (h, w) pairs.  ``out``: fp32
+    contiguous [B, N, OH, OW]; allocated when None.  Counts in ``LINEAR_CALLS``.  Asynchronous on
+    the current stream; there is no CPU fallback."""
+    global LINEAR_CALLS
+    bits = int(bits)
+    if not 2 <= bits <= 8:
+        raise ValueError("bits must be 2..8, got %d" % bits)
+    _on_gpu("x", x, "a float32 tensor")
+    if x.dtype != torch.float32:
+        raise TypeError("x: float32 on the GPU")
+    (KH, KW), (sh, sw) = mx._pair(kernel_size, "kernel_size"), mx._pair(stride, "stride")
+    (ph, pw), (dh, dw) = mx._pair(padding, "padding"), mx._pair(dilation, "dilation")
+    if min(KH, KW, sh, sw, dh, dw) < 1 or min(ph, pw) < 0:
+        raise ValueError("kernel_size, stride and dilation must be >= 1 and padding >= 0")
+    if x.dim() != 4 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError("x must be a contiguous [B, C, H, W] tensor, got %s with strides %s" % (tuple(x.shape), tuple(x.stride())))
+    B, Cin, H, W = x.shape
+    K = KH * KW
+    if K > DW_MAX_TAPS:
+        raise ValueError("KH * KW must be <= %d (a tap mask is one 64-bit word), got %d" % (DW_MAX_TAPS, K))
+    d = _lib.IntDwConv2dDesc()
+    _range_args(d, min_dev, max_dev, min_value, max_value, scale_f32)
+    N = _b_args(d, b_codes, b_scale, b_zero, K, bool(b_packed))
+    if N % Cin:
+        raise ValueError("b_codes holds %d rows of %d, no multiple of the %d input channels" % (N, K, Cin))
+    OH, OW = mx.conv_out_size(H, KH, sh, ph, dh), mx.conv_out_size(W, KW, sw, pw, dw)
+    if OH < 1 or OW < 1:
+        raise ValueError("the kernel %s (dilation %s) does not fit the padded input %s" % ((KH, KW), (dh, dw), (H + 2 * ph, W + 2 * pw)))
+    dev = x.device
+    if bias is not None:
+        _lib.require_device(bias)
+        if bias.numel() != N:
+            raise ValueError("bias holds %d elements, %d needed" % (bias.numel(), N))
+    if out is None:
+        out = torch.empty((B, N, OH, OW), dtype=torch.float32, device=dev)
+    else:
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32:
+            raise TypeError("out: float32 on the GPU")
+        if tuple(out.shape) != (B, N, OH, OW) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous [%d, %d, %d, %d] tensor" % (B, N, OH, OW))
+    for t in (min_dev, max_dev, b_codes, b_scale, b_zero, bias, out):
+        if t is not None and t.device != dev:
+            raise ValueError("every tensor of an int_dwconv2d call must live on one device")
+    d.x, d.out = x.data_ptr(), out.data_ptr()
+    d.bias = bias.data_ptr() if bias is not None else None
+    d.B, d.C, d.H, d.W, d.mult, d.KH, d.KW = B, Cin, H, W, N // Cin, KH, KW
+    d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w = sh, sw, ph, pw, dh, dw
+    d.x_bits, d.x_symmetric = bits, int(bool(symmetric))
+    _lib.check(_lib.load().dfq_int_dwconv2d(C.byref(d), _lib.raw_stream(dev)), "dfq_int_dwconv2d", ValueError)
     LINEAR_CALLS += 1
     return out

@@ -70,6 +70,13 @@ Same flags and stage order; the transforms run on the GPU.  Additive flags:
                        gathers the im2col rows from the NCHW input, quantizes them and stores
                        NCHW; a padding tap is the real value 0, as in F.conv2d.  Grouped and
                        depthwise convolutions stay on fp32.  Needs --int_matmul
+  --int_matmul_depthwise  with --int_matmul_conv: every depthwise convolution (groups ==
+                       in_channels, zero padding mode, at most 64 taps) multiplies on the packed
+                       8-bit dot instruction (intmm.int_dwconv2d, dfq_int_dwconv2d): one launch
+                       quantizes each input element once, keeps the code bytes in LDS and stores
+                       NCHW, so every Conv2d / Linear product of MobileNetV2 and DeepLab is an
+                       integer one.  Other grouped convolutions stay on fp32.  Needs
+                       --int_matmul_conv
 
 Example (README.md:137 of the reference):
   python -m data_free_quantization_amd.main_dfq --task cls --relu --equalize --absorption \
@@ -153,6 +160,9 @@ def get_argument(argv=None):
     p.add_argument("--int_matmul_conv", action="store_true",
                    help="with --int_matmul: k x k convolutions (groups == 1) multiply on the i8 matrix instruction too, "
                         "their im2col rows gathered and quantized inside the kernel")
+    p.add_argument("--int_matmul_depthwise", action="store_true",
+                   help="with --int_matmul_conv: depthwise convolutions multiply on the packed 8-bit dot instruction, "
+                        "their input quantized once per element inside the kernel")
     p.add_argument("--mx_scale_search", action="store_true",
                    help="MX weights: per block, the better of the floor rule's scale and the next one up by "
                         "the block's own quantization noise")
@@ -165,6 +175,8 @@ def get_argument(argv=None):
         p.error("--mx_matmul_conv needs --mx_matmul")
     if args.int_matmul_conv and not args.int_matmul:
         p.error("--int_matmul_conv needs --int_matmul")
+    if args.int_matmul_depthwise and not args.int_matmul_conv:
+        p.error("--int_matmul_depthwise needs --int_matmul_conv")
     if args.int_matmul and args.mx_matmul is not None:
         p.error("--int_matmul conflicts with --mx_matmul")
     if args.int_matmul and (not args.quantize or args.weight_format != "int"):
@@ -379,7 +391,7 @@ def main(argv=None):
         import contextlib
         from .utils.quantize import frozen_weights, int_matmul_forward, mx_matmul_forward
         scope = (mx_matmul_forward(args.mx_matmul, fused=args.mx_matmul_fused, conv=args.mx_matmul_conv) if args.mx_matmul is not None
-                 else int_matmul_forward(conv=args.int_matmul_conv) if args.int_matmul else contextlib.nullcontext())
+                 else int_matmul_forward(conv=args.int_matmul_conv, depthwise=args.int_matmul_depthwise) if args.int_matmul else contextlib.nullcontext())
         with frozen_weights(), scope:
             accuracy = inference_all(model, args.task, args)
         print(f"Inference time is {time.time() - start} seconds")

@@ -409,10 +409,11 @@ def mx_matmul_forward(act_format: str = "mxfp8", fused: bool = False, conv: bool
 
 _INT_MATMUL = False   # an int_matmul_forward() scope is open
 _INT_CONV = False     # that scope's convolutions multiply through intmm.int_conv2d
+_INT_DW = False       # and its depthwise convolutions through intmm.int_dwconv2d
 
 
 @contextlib.contextmanager
-def int_matmul_forward(conv: bool = False):
+def int_matmul_forward(conv: bool = False, depthwise: bool = False):
     """Inference with the integer layers' products on the i8 matrix instruction: inside this
     scope a Quant* layer whose ``weight_format`` mark is "int" (the default) multiplies through
     ``intmm.int_linear`` -- its weight's integer codes times its input's activation codes --
@@ -438,15 +439,25 @@ def int_matmul_forward(conv: bool = False):
     codes, the range and the bias are the same; each call counts in ``intmm.LINEAR_CALLS``.  An
     unpadded 1x1 layer gives the bits it gives with ``conv=False``.  Grouped and depthwise
     convolutions, string padding and other padding modes stay on ``F.conv2d``.  The scope nests
-    and restores like ``mx_matmul_forward``'s."""
+    and restores like ``mx_matmul_forward``'s.
+    ``depthwise`` (needs ``conv``, else ValueError): every QuantConv2d / QConv2d with groups ==
+    in_channels > 1, out_channels a multiple of in_channels, padding_mode "zeros", an int or tuple
+    padding and KH * KW <= ``intmm.DW_MAX_TAPS`` multiplies through ``intmm.int_dwconv2d``
+    (``dfq_int_dwconv2d``): one launch on the packed 8-bit dot instruction that quantizes each
+    input element once.  The weight codes are the same ``fake_quant(weight.reshape(N, -1))`` --
+    rows of KH * KW -- and a QConv2d's scaled temporary weight takes the route like its k x k
+    one (its codes are re-derived every forward).  Other grouped convolutions (1 < groups <
+    in_channels) stay on ``F.conv2d``."""
     from .. import intmm
-    global _INT_MATMUL, _INT_CONV
-    prev, _INT_MATMUL, _INT_CONV = (_INT_MATMUL, _INT_CONV), True, bool(conv)
+    global _INT_MATMUL, _INT_CONV, _INT_DW
+    if depthwise and not conv:
+        raise ValueError("int_matmul_forward(depthwise=True) needs conv=True")
+    prev, _INT_MATMUL, _INT_CONV, _INT_DW = (_INT_MATMUL, _INT_CONV, _INT_DW), True, bool(conv), bool(depthwise)
     intmm.reset_linear_calls()
     try:
         yield
     finally:
-        _INT_MATMUL, _INT_CONV = prev
+        _INT_MATMUL, _INT_CONV, _INT_DW = prev
 
 
 class _QuantWeightMixin:
@@ -532,13 +543,14 @@ class _QuantWeightMixin:
         return self._mx_product(x2d, weight, bias, qweight, qbias, fmt).view(*input.shape[:-1], -1)
 
     def _int_routed(self):
-        """The layer's product runs through intmm.int_linear or intmm.int_conv2d (int_matmul_forward)."""
+        """The layer's product runs through intmm.int_linear, intmm.int_conv2d or intmm.int_dwconv2d
+        (int_matmul_forward)."""
         if not _INT_MATMUL or self.__dict__.get("weight_format", "int") != "int":
             return False
         if self.num_bits > 8 or self.quant.num_bits > 8:
             return False
         if isinstance(self, nn.Conv2d):
-            return self._int_conv_routed() or (
+            return self._int_conv_routed() or self._int_dw_routed() or (
                 tuple(self.kernel_size) == (1, 1) and self.groups == 1 and not isinstance(self.padding, str) and
                 tuple(self.padding) == (0, 0))
         return True
@@ -548,6 +560,13 @@ class _QuantWeightMixin:
         from .. import intmm
         return (_INT_CONV and self.groups == 1 and self.padding_mode == "zeros" and not isinstance(self.padding, str) and
                 self.in_channels * self.kernel_size[0] * self.kernel_size[1] <= intmm.MAX_K)
+
+    def _int_dw_routed(self):
+        """The depthwise convolution multiplies through intmm.int_dwconv2d (int_matmul_forward(conv=True, depthwise=True))."""
+        from .. import intmm
+        return (_INT_DW and _INT_CONV and self.groups > 1 and self.groups == self.in_channels and
+                self.out_channels % self.in_channels == 0 and self.padding_mode == "zeros" and
+                not isinstance(self.padding, str) and self.kernel_size[0] * self.kernel_size[1] <= intmm.DW_MAX_TAPS)
 
     def _int_operands(self, x, weight, bias):
         """The range the observer just quantized the input with, and the weight's integer codes,
@@ -575,8 +594,13 @@ class _QuantWeightMixin:
         return intmm.int_linear(x2d, *wq, x2d.shape[1], bits=self.quant.num_bits, min_dev=rng[0], max_dev=rng[1], bias=qbias)
 
     def _int_conv(self, input, weight, bias, qbias):
-        """The layer's product: intmm.int_conv2d on the NCHW input (conv=True) or the 1x1 path."""
+        """The layer's product: intmm.int_dwconv2d (depthwise=True), intmm.int_conv2d on the NCHW
+        input (conv=True) or the 1x1 path."""
         from .. import intmm
+        if self._int_dw_routed():
+            rng, wq = self._int_operands(input, weight, bias)
+            return intmm.int_dwconv2d(input.detach().contiguous(), *wq, self.kernel_size, self.stride, self.padding, self.dilation,
+                                      bits=self.quant.num_bits, min_dev=rng[0], max_dev=rng[1], bias=qbias)
         if not self._int_conv_routed():
             return self._int_conv1x1(input, weight, bias, qbias)
         rng, wq = self._int_operands(input, weight, bias)

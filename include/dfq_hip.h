@@ -825,6 +825,85 @@ typedef struct dfq_int_conv2d_desc {
 } dfq_int_conv2d_desc;
 int dfq_int_conv2d(const dfq_int_conv2d_desc* d, void* stream);
 
+/* ---- integer depthwise convolution in one launch (packed 8-bit dot products) ----
+ * dfq_int_conv2d's statement for groups == C: output channel n of N = C * mult reads input
+ * channel c = n / mult and nothing else, so K = KH * KW.  With
+ *   k = i * KW + j,
+ *   v[b,oh,ow][k] = 1 where the tap (oh * stride_h - pad_h + i * dil_h, ow * stride_w - pad_w + j * dil_w)
+ *                   lies inside the image, else 0,
+ * qa the code dfq_fake_quant_given's quantizer gives x[b][c] at that tap (dfq_int_linear's: the
+ * range from min_dev / max_dev or given_min / given_max, x_bits 2..8, x_symmetric, sa = s,
+ * za = min, +0 when symmetric, always present) and qb [N, K] the weight's codes -- the order
+ * [N, 1, KH, KW] is stored in; bytes, or [N, K / 2] nibbles with DFQ_INT_B_PACK4 (K even: a
+ * 3 x 3 kernel is refused when packed) -- the exact integers
+ *   P[b,n,oh,ow]  = sum_k v qa qb     Sa[b,c,oh,ow] = sum_k v qa
+ *   Sb[n,oh,ow]   = sum_k v qb        T[oh,ow]      = sum_k v
+ * give
+ *   acc  = ((double)sa * (double)sb[n]) * (double)P
+ *   acc += ((double)sa * (double)zb[n]) * (double)Sa       -- if b_zero
+ *   acc += ((double)za * (double)sb[n]) * (double)Sb
+ *   acc += ((double)za * (double)zb[n]) * (double)T        -- if b_zero
+ *   acc += (double)bias[n]                                 -- if bias
+ *   out[b][n][oh][ow] = (float)acc
+ * in fp64, one IEEE operation per step in this order, no contraction: bit for bit a numpy
+ * float64 statement, and bit for bit dfq_int_conv2d on channel c alone with rows c * mult ..
+ * (c + 1) * mult - 1 of B.  A padding tap has the real value 0 (absent from every sum, not the
+ * code of 0.0); an output wholly in padding stores (float)bias[n] (0 without a bias).
+ * A workgroup owns a tile of at most DFQ_INT_DW_TILE_H x DFQ_INT_DW_TILE_W outputs of one
+ * (b, c) plane -- or, where a plane fits one tile, several whole planes -- for all mult output
+ * channels: it reads the tile's input footprint with its halo once, quantizes every element
+ * once and keeps the code bytes (never the fp32 values) in LDS, 0 where the footprint leaves
+ * the image.  The products run on the packed 8-bit dot instruction (v_dot4c_i32_i8, signed x
+ * signed: unsigned codes enter as q - 128 on the taps inside the image and the offset is folded
+ * back in integers with T where dfq_int_gemm has K); sum_k v qa and sum_k v qb come from the same
+ * instruction against an all-ones word and a 0 / 1 mask word.  One accumulator per output
+ * element, the taps in order, no atomics, no workspace: the same bits from run to run.
+ * Asynchronous on `stream`, no host wait.  Checked on the host before any device call:
+ * DFQ_ERR_INVALID for a NULL x, b_codes, b_scale or out, unknown flags, non-zero reserved or
+ * reserved2, b_signed or x_symmetric not 0 / 1, x_bits outside 2..8, an extent (B, C, H, W,
+ * mult, KH, KW), stride or dilation < 1, a padding < 0, any of these or C * mult above 2^28,
+ * C * H * W or N * OH * OW at or above 2^31, B * OH * OW above 2^31, x, out, bias, min_dev,
+ * max_dev, b_scale or b_zero not 4-B aligned, b_codes not 16-B aligned; DFQ_ERR_SHAPE when OH or
+ * OW comes out < 1; DFQ_ERR_UNSUPPORTED for KH * KW > DFQ_INT_DW_MAX_TAPS, packed B with an odd
+ * K, a single output's footprint ((KH - 1) dil_h + 1) * ((KW - 1) dil_w + 1) beyond
+ * DFQ_INT_DW_LDS_BYTES, a grid beyond int32. */
+#define DFQ_INT_DW_MAX_TAPS   64     /* the largest KH * KW (7 x 7 = 49 fits): a tap mask is one 64-bit word */
+#define DFQ_INT_DW_TILE_H     32     /* the largest output tile of a workgroup */
+#define DFQ_INT_DW_TILE_W     64
+#define DFQ_INT_DW_LDS_BYTES  16384  /* the code bytes a workgroup keeps */
+typedef struct dfq_int_dwconv2d_desc {
+    const float* x;         /* fp32 [B, C, H, W], contiguous; 4-B aligned */
+    const float* min_dev;   /* device float or NULL: the range's min (else given_min) */
+    const float* max_dev;   /* device float or NULL: the range's max (else given_max) */
+    const void*  b_codes;   /* [N, K] bytes, or [N, K / 2] with DFQ_INT_B_PACK4; N = C * mult, K = KH * KW */
+    const float* b_scale;   /* device, 1 or N values */
+    const float* b_zero;    /* device, 1 or N values, or NULL (0) */
+    const float* bias;      /* [N] or NULL */
+    float*       out;       /* fp32 [B, N, OH, OW], contiguous */
+    double       given_min;
+    double       given_max;
+    int64_t      B;
+    int64_t      C;
+    int64_t      H;
+    int64_t      W;
+    int64_t      mult;      /* output channels per input channel: N = C * mult */
+    int64_t      KH;
+    int64_t      KW;
+    int64_t      stride_h;
+    int64_t      stride_w;
+    int64_t      pad_h;
+    int64_t      pad_w;
+    int64_t      dil_h;
+    int64_t      dil_w;
+    int32_t      x_bits;    /* 2..8 */
+    int32_t      x_symmetric;
+    int32_t      b_signed;
+    int32_t      flags;     /* DFQ_INT_B_PACK4 | DFQ_INT_B_PER_ROW | DFQ_SCALE_F32 */
+    int32_t      reserved;  /* 0 */
+    int32_t      reserved2; /* 0 */
+} dfq_int_dwconv2d_desc;
+int dfq_int_dwconv2d(const dfq_int_dwconv2d_desc* d, void* stream);
+
 /* ---- high-bias absorption (bias_absorption.py:147-197) ------------------
  * c = max(bn_b - N*bn_w, 0) (bn_* = the BN's fake_weight / fake_bias);
  * b2[o] += sum_i (sum_k W2[o,i,k]) * c[g*i2 + i];  b1 -= c;  bn_b -= c.
