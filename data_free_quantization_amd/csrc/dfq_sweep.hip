@@ -33,6 +33,7 @@
 #include <cstdlib>
 #include <new>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace dfq {
@@ -52,17 +53,6 @@ struct LdsLayout {
 };
 
 __device__ __forceinline__ bool is_sym(int mode) { return mode == DFQ_TENSOR_SYM || mode == DFQ_CHANNEL_SYM; }
-
-template <bool NT, typename V>
-__device__ __forceinline__ void st(V* p, const V& v);
-
-__device__ __forceinline__ void store_code(void* codes, int cb, int64_t idx, float q) {
-    if (cb == 1) {
-        st<false>(static_cast<int8_t*>(codes) + idx, (int8_t)(int)q);  // same bits as uint8 for 0..255
-    } else {
-        st<false>(static_cast<int16_t*>(codes) + idx, (int16_t)(int)q);
-    }
-}
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) void gbl_void_t;
@@ -99,7 +89,6 @@ __device__ __forceinline__ void glds4_asm(const float* g, float* lds_base) {
 // Stores through address_space(1) pointers: the descriptor fields are generic
 // pointers, and a flat_store also counts on lgkmcnt, so every LDS wait would
 // drain the wave's outstanding stores.  global_store_* does not.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 template <bool NT, typename V>
 __device__ __forceinline__ void st(V* p, const V& v) {
     if constexpr (sizeof(V) == 16) {
@@ -111,6 +100,13 @@ __device__ __forceinline__ void st(V* p, const V& v) {
         DFQ_GLOBAL V* g = (DFQ_GLOBAL V*)p;
         if constexpr (NT) __builtin_nontemporal_store(v, g);
         else *g = v;
+    }
+}
+__device__ __forceinline__ void store_code(void* codes, int cb, int64_t idx, float q) {
+    if (cb == 1) {
+        st<false>(static_cast<int8_t*>(codes) + idx, (int8_t)(int)q);  // same bits as uint8 for 0..255
+    } else {
+        st<false>(static_cast<int16_t*>(codes) + idx, (int16_t)(int)q);
     }
 }
 __device__ __forceinline__ float ld(const float* p) { return *(const DFQ_GLOBAL float*)p; }
@@ -332,8 +328,46 @@ __device__ __forceinline__ void quant_vec4_c(int cb, int em, const DevTensor& T,
     }
 }
 
+// Step 4, the KH*KW error sums of a task whose eps are in ``data``: E[p] = sum_k
+// eps[p*khw + k] in ATen's order (torch.sum(eps.view(O, I, -1), -1)).  ESPEC: the
+// kernel sizes that get a compile-time length, so the ATen cascade unrolls into
+// straight adds -- 2: 3x3 / 7x7 / 5x5 / 2x2, 1: 3x3, 0: none.
+template <int ESPEC>
+__device__ __forceinline__ void khw_error_sums(const DevTensor& T, const float* data, int n, int64_t base, int lane) {
+    const int khw = T.khw;
+    const int np = n / khw;
+    const int64_t pbase = base / khw;
+    auto esums = [&](auto kconst) {
+        constexpr int K = decltype(kconst)::value;
+        for (int pi = lane; pi < np; pi += kWave) {
+            const float* e = data + pi * K;
+            st<false>(T.esum + pbase + pi, aten_inner_sum([&](int64_t k) { return e[k]; }, (int64_t)K));
+        }
+    };
+    auto generic = [&]() {
+        for (int pi = lane; pi < np; pi += kWave) {
+            const float* e = data + pi * khw;
+            st<false>(T.esum + pbase + pi, aten_inner_sum([&](int64_t k) { return e[k]; }, khw));
+        }
+    };
+    if constexpr (ESPEC == 2) {
+        switch (khw) {
+            case 9: esums(std::integral_constant<int, 9>{}); break;     // 3x3
+            case 49: esums(std::integral_constant<int, 49>{}); break;   // 7x7
+            case 25: esums(std::integral_constant<int, 25>{}); break;   // 5x5
+            case 4: esums(std::integral_constant<int, 4>{}); break;     // 2x2
+            default: generic();
+        }
+    } else if constexpr (ESPEC == 1) {
+        if (khw == 9) esums(std::integral_constant<int, 9>{});
+        else generic();
+    } else {
+        generic();
+    }
+}
+
 // Steps 2-4 on a chunk that has landed in ``data``.
-// ESPEC: compile-time KH*KW error sums -- 2: 3x3/5x5/7x7/2x2, 1: 3x3, 0: none
+// ESPEC: khw_error_sums' compile-time lengths.
 // goff >= 0: a row-group piece whose per-row parameters are already in ls / lmn
 // (local row 0 = the row holding the piece's first element, goff = that element's
 // offset inside it).
@@ -608,40 +642,10 @@ __device__ __forceinline__ void compute_task(const DevTensor& T, const DevTask& 
     }
 
     if (tlm) tlm[1] = wall_clock64();   // quantize loop issued
-    // 4. KHW error sums: E[p] = sum_k eps[p*khw + k] in ATen's order
+    // 4. KH*KW error sums
     if (want_e && khw > 1) {
         wave_lds_sync();
-        const int np = n / khw;
-        const int64_t pbase = base / khw;
-        // torch.sum(eps.view(O, I, -1), -1) order; the common kernel sizes get a
-        // compile-time length so the ATen cascade unrolls into straight adds.
-        auto esums = [&](auto kconst) {
-            constexpr int K = decltype(kconst)::value;
-            for (int pi = lane; pi < np; pi += kWave) {
-                const float* e = data + pi * K;
-                st<false>(T.esum + pbase + pi, aten_inner_sum([&](int64_t k) { return e[k]; }, (int64_t)K));
-            }
-        };
-        auto generic = [&]() {
-            for (int pi = lane; pi < np; pi += kWave) {
-                const float* e = data + pi * khw;
-                st<false>(T.esum + pbase + pi, aten_inner_sum([&](int64_t k) { return e[k]; }, khw));
-            }
-        };
-        if constexpr (ESPEC == 2) {
-            switch (khw) {
-                case 9: esums(std::integral_constant<int, 9>{}); break;     // 3x3
-                case 49: esums(std::integral_constant<int, 49>{}); break;   // 7x7
-                case 25: esums(std::integral_constant<int, 25>{}); break;   // 5x5
-                case 4: esums(std::integral_constant<int, 4>{}); break;     // 2x2
-                default: generic();
-            }
-        } else if constexpr (ESPEC == 1) {
-            if (khw == 9) esums(std::integral_constant<int, 9>{});
-            else generic();
-        } else {
-            generic();
-        }
+        khw_error_sums<ESPEC>(T, data, n, base, lane);
     }
     wave_lds_sync();  // LDS is reused by this wave's next task
 }
@@ -744,37 +748,9 @@ __device__ __forceinline__ bool compute_task_split(const DevTensor& T, const Dev
     vm_wait_le(((h * len >> 2) + 2 * kWave - 1) / (2 * kWave));   // every load of the task has landed
     wave_lds_sync();
     rows(h, nrows);
-    if (want_e && khw > 1) {   // 4. KHW error sums over the whole task (compute_task's step 4)
+    if (want_e && khw > 1) {   // the KH*KW error sums run over the whole task
         wave_lds_sync();
-        const int np = n / khw;
-        const int64_t pbase = base / khw;
-        auto esums = [&](auto kconst) {
-            constexpr int K = decltype(kconst)::value;
-            for (int pi = lane; pi < np; pi += kWave) {
-                const float* e = data + pi * K;
-                st<false>(T.esum + pbase + pi, aten_inner_sum([&](int64_t k) { return e[k]; }, (int64_t)K));
-            }
-        };
-        auto generic = [&]() {
-            for (int pi = lane; pi < np; pi += kWave) {
-                const float* e = data + pi * khw;
-                st<false>(T.esum + pbase + pi, aten_inner_sum([&](int64_t k) { return e[k]; }, khw));
-            }
-        };
-        if constexpr (ESPEC == 2) {
-            switch (khw) {
-                case 9: esums(std::integral_constant<int, 9>{}); break;
-                case 49: esums(std::integral_constant<int, 49>{}); break;
-                case 25: esums(std::integral_constant<int, 25>{}); break;
-                case 4: esums(std::integral_constant<int, 4>{}); break;
-                default: generic();
-            }
-        } else if constexpr (ESPEC == 1) {
-            if (khw == 9) esums(std::integral_constant<int, 9>{});
-            else generic();
-        } else {
-            generic();
-        }
+        khw_error_sums<ESPEC>(T, data, n, base, lane);
     }
     wave_lds_sync();   // LDS is reused by this wave's next task
     return true;
@@ -995,40 +971,27 @@ sweep_main_kernel(const DevTensor* __restrict__ tensors, const DevTask* __restri
 // ---------------------------------------------------------------------------
 // Host: kernel selection, plans (the planner itself: dfq_sweep_plan.cpp).
 // ---------------------------------------------------------------------------
-static int lds_bytes(const Variant& V) {
-    return 4 * kWavesPerBlock * ((V.prefetch ? 2 : 1) * V.chunk + 3 * V.max_rows);
-}
-
 using MainKernel = void (*)(const DevTensor*, const DevTask*, int64_t, const uint32_t*, const uint32_t*);
 
+// Row I of kVariants as a kernel: the row is the whole truth about its variant.
+template <int I>
+static MainKernel variant_kernel() {
+    constexpr Variant V = kVariants[I];
+    return sweep_main_kernel<V.chunk, V.max_rows, V.prefetch, V.nt, V.espec, V.timeline, V.screen, V.fast, V.split>;
+}
+template <int... I>
+static MainKernel variant_kernel(int variant, std::integer_sequence<int, I...>) {
+    static const MainKernel table[] = {variant_kernel<I>()...};
+    return table[variant >= 0 && variant < kNumVariants ? variant : 0];
+}
+
 static MainKernel main_kernel(int variant) {
-#define DFQ_V(i) kVariants[i].chunk, kVariants[i].max_rows, kVariants[i].prefetch
 #ifndef DFQ_DIAGNOSTICS
     // the product library carries the default variant and the small-list one
-    if (variant == kSmallVariant) return sweep_main_kernel<DFQ_V(kSmallVariant), true, 1>;
-    return sweep_main_kernel<DFQ_V(kDefaultVariant), true, 1, false, true, true, kDefaultVariant == 16>;
+    return variant == kSmallVariant ? variant_kernel<kSmallVariant>() : variant_kernel<kDefaultVariant>();
 #else
-    switch (variant) {
-        case 1: return sweep_main_kernel<DFQ_V(1)>;
-        case 2: return sweep_main_kernel<DFQ_V(2)>;
-        case 3: return sweep_main_kernel<DFQ_V(3)>;
-        case 4: return sweep_main_kernel<DFQ_V(4)>;
-        case 5: return sweep_main_kernel<DFQ_V(5), true>;
-        case 6: return sweep_main_kernel<DFQ_V(6), true, 1>;
-        case 7: return sweep_main_kernel<DFQ_V(7), true, 0>;
-        case 8: return sweep_main_kernel<DFQ_V(8), true, 1>;
-        case 9: return sweep_main_kernel<DFQ_V(9), true, 1>;
-        case 10: return sweep_main_kernel<DFQ_V(10), true, 1>;
-        case 11: return sweep_main_kernel<DFQ_V(11), true, 1>;
-        case 12: return sweep_main_kernel<DFQ_V(12), true, 0>;
-        case 13: return sweep_main_kernel<DFQ_V(13), true, 1, true>;
-        case 14: return sweep_main_kernel<DFQ_V(14), true, 1, false, false>;
-        case 15: return sweep_main_kernel<DFQ_V(15), true, 1, false, true, false>;
-        case 16: return sweep_main_kernel<DFQ_V(16), true, 1, false, true, true, true>;
-        default: return sweep_main_kernel<DFQ_V(0)>;
-    }
+    return variant_kernel(variant, std::make_integer_sequence<int, kNumVariants>{});
 #endif
-#undef DFQ_V
 }
 
 // Grid: up to 64 blocks per CU (16384 blocks), far more than are resident (4-5

@@ -18,34 +18,40 @@ namespace dfq {
 
 constexpr int kWavesPerBlock = 4;
 
-// Kernel variants (chunk elements per wave task, rows per whole-row task, LDS-DMA
-// prefetch of the next task).  The task table is built for the plan's variant.
+// Kernel variants: each row is the whole truth about its variant.  The planner reads
+// the first three fields (the task table is built for the plan's variant); the rest
+// are sweep_main_kernel's template arguments, instantiated from the row.
 struct Variant {
-    int chunk;
-    int max_rows;
-    bool prefetch;
+    int chunk;       // elements per wave task
+    int max_rows;    // rows of one whole-row task; the host caps rows per task at max(64 (one short row
+                     // per lane), chunk / 32) (build()): 3 * max_rows floats of row parameters per wave
+    bool prefetch;   // LDS-DMA of the wave's next task in flight during compute (two chunk buffers)
+    bool nt;         // non-temporal loads and stores
+    int espec;       // KH*KW sums with a compile-time length: 2 3x3 / 7x7 / 5x5 / 2x2, 1 3x3, 0 none
+    bool timeline;   // per-task timestamps and the ablation word (diagnostics: dfq_debug_timeline / _ablate)
+    bool screen;     // the screened reciprocal quantize; false: the IEEE divide on every element
+    bool fast;       // the fixed-form quantize loop; false: the generic one (flags tested per float4)
+    bool split;      // whole-row tasks in two row batches (compute_task_split)
 };
-// max_rows: rows of one whole-row task; the host caps rows per task at
-// max(64 (one short row per lane), chunk / 32) (build()), so the per-row
-// parameter arrays (scale, min) take 2 * max_rows floats per wave.
 constexpr Variant kVariants[] = {
-    {2048, 64, false},    // 0: 8.5 KB LDS / wave, 16 waves / CU
-    {1024, 64, true},     // 1: 2 x 4 KB, next task's DMA in flight during compute
-    {2048, 64, true},     // 2: 2 x 8 KB
-    {1024, 64, false},    // 3: 4.5 KB / wave
-    {4096, 128, false},   // 4: 17 KB / wave, 8 waves / CU
-    {2048, 64, false},    // 5: variant 0 with non-temporal loads and stores
-    {2048, 64, false},    // 6: variant 5, KH*KW sums specialised for 3x3 only (fewer VGPRs)
-    {2048, 64, false},    // 7: variant 5, generic KH*KW sums only
-    {2560, 80, false},    // 8: variant 6 with 2560-element tasks (12 waves / CU)
-    {1024, 64, false},    // 9: variant 6 with 1024-element tasks
-    {1536, 64, false},    // 10: variant 6 with 1536-element tasks
-    {1024, 64, true},     // 11: 1024-element tasks, next task's DMA in flight, NT
-    {1024, 64, false},    // 12: variant 9 with the generic E sums (fewer VGPRs)
-    {2048, 64, false},    // 13: variant 6 + per-task timestamps (diagnostics: dfq_debug_timeline)
-    {2048, 64, false},    // 14: variant 6 with the IEEE divide on every element (round-2 arithmetic)
-    {2048, 64, false},    // 15: variant 6 with the generic quantize loop (flags tested per float4; round 3)
-    {2048, 64, false},    // 16: variant 6 with whole-row tasks in two row batches (compute_task_split)
+    //                   nt     E  tl     screen fast  split
+    {2048, 64, false,  false, 2, false, true, true, false},   // 0: 8.5 KB LDS / wave, 16 waves / CU
+    {1024, 64, true,   false, 2, false, true, true, false},   // 1: 2 x 4 KB, next task's DMA in flight
+    {2048, 64, true,   false, 2, false, true, true, false},   // 2: 2 x 8 KB
+    {1024, 64, false,  false, 2, false, true, true, false},   // 3: 4.5 KB / wave
+    {4096, 128, false, false, 2, false, true, true, false},   // 4: 17 KB / wave, 8 waves / CU
+    {2048, 64, false,  true, 2, false, true, true, false},    // 5: variant 0, non-temporal
+    {2048, 64, false,  true, 1, false, true, true, false},    // 6: variant 5, 3x3 sums only (fewer VGPRs)
+    {2048, 64, false,  true, 0, false, true, true, false},    // 7: variant 5, generic sums only
+    {2560, 80, false,  true, 1, false, true, true, false},    // 8: variant 6, 2560-element tasks (12 waves / CU)
+    {1024, 64, false,  true, 1, false, true, true, false},    // 9: variant 6, 1024-element tasks
+    {1536, 64, false,  true, 1, false, true, true, false},    // 10: variant 6, 1536-element tasks
+    {1024, 64, true,   true, 1, false, true, true, false},    // 11: variant 9 with the prefetch
+    {1024, 64, false,  true, 0, false, true, true, false},    // 12: variant 9, generic sums (fewer VGPRs)
+    {2048, 64, false,  true, 1, true, true, true, false},     // 13: variant 6 + timeline and ablations
+    {2048, 64, false,  true, 1, false, false, true, false},   // 14: variant 6, IEEE divide everywhere (round 2)
+    {2048, 64, false,  true, 1, false, true, false, false},   // 15: variant 6, generic quantize loop (round 3)
+    {2048, 64, false,  true, 1, false, true, true, true},     // 16: variant 6 in two row batches
 };
 constexpr int kNumVariants = (int)(sizeof(kVariants) / sizeof(kVariants[0]));
 // DevTask .nrows <= kGroupTag: a row-group piece of R = kGroupTag - nrows + 1 rows
