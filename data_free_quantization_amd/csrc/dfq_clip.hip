@@ -41,7 +41,7 @@ __device__ __forceinline__ float clip_clamp(float x, float lo, float hi) { retur
 struct ClipCand {
     float lo, hi;
     QParams p;
-    float rs;   // rcp(p.s) for the screened quotient
+    float rs, band;   // screen_rcp(p.s) for the screened quotient
 };
 __device__ __forceinline__ ClipCand clip_cand(float mn, float mx, int k, const ClipJob& J) {
     ClipCand c;
@@ -49,7 +49,7 @@ __device__ __forceinline__ ClipCand clip_cand(float mn, float mx, int k, const C
     c.lo = a * mn;
     c.hi = a * mx;
     c.p = make_qparams(clip_clamp(mn, c.lo, c.hi), clip_clamp(mx, c.lo, c.hi), J.bits, J.sym != 0, 0, 0.0, 0.0);
-    c.rs = __builtin_amdgcn_rcpf(c.p.s);
+    c.rs = screen_rcp(c.p.s, c.band);
     return c;
 }
 
@@ -72,7 +72,7 @@ __device__ __forceinline__ double clip_noise(const float* xs, int len, int j, in
             x[u] = xs[i < len ? i : len - 1];   // always inside the copy (no branch around the read); masked below
             cl[u] = clip_clamp(x[u], c.lo, c.hi);
             bool nd;
-            t[u] = qdq_screen(cl[u], c.p, c.rs, nd);
+            t[u] = qdq_screen(cl[u], c.p, c.rs, c.band, nd);
             need |= nd;
         }
         if (__builtin_amdgcn_ballot_w64(need)) {   // wave-uniform, rare: the IEEE divide decides

@@ -237,17 +237,39 @@ __device__ __forceinline__ float qdq(float x, const QParams& p, float& q) {
 // from any half-integer) and t is within the error bound of a beyond it, so
 // clamp(t) rounds to the same end point; NaN / inf clamp as in qdq.  Otherwise
 // -- ties and near-ties, ~1e-5 of the elements at INT8 -- the IEEE divide
-// decides.  The dequantize (q * s + mn) is unchanged.  rs = __builtin_amdgcn_rcpf(s).
+// decides.  The dequantize (q * s + mn) is unchanged.  rs and band = screen_rcp(s).
 // The caller branches on a WAVE-uniform "any lane needs it" (ballot), so the
 // divide is neither executed nor if-converted into every element's path: ~8
 // VALU fewer per element (the sweep is issue-bound at ~500 G elements/s), and the
 // one clamp serves both the test and the rounding.
+//
+// The reciprocal alone, where a loop takes it per element and its band was chosen with
+// the row's parameters (screen_rcp / screen_band there).
+__device__ __forceinline__ float screen_rs(float s) { return __builtin_amdgcn_rcpf(s); }
+// The screen's reciprocal and band factor of a scale, once per row (wave-uniform).
+// The error bound above needs a normal 1 / s.  v_rcp_f32 flushes a subnormal
+// result to 0 (measured on gfx950: rcp(2^126) = 2^-126, rcp(nextafter(2^126)) = 0),
+// so for s > 2^126 -- a 2-bit range of fp32 data near +-1e38, or a given range of
+// doubles beyond fp32 -- a would be 0 for every x, far from every half-integer,
+// and no element would take the divide.  There band = +inf: |d| > |t| inf is false
+// for every t (inf, or NaN at t = 0), so every element of the row takes the IEEE
+// divide.  Everywhere else band = 2^-20.
+__device__ __forceinline__ float screen_rcp(float s, float& band) {
+    const float rs = screen_rs(s);
+    band = __builtin_isnormal(rs) ? 0x1p-20f : INFINITY;
+    return rs;
+}
+// One band for the rows a wave quantizes together (the sweep's tasks): +inf when any
+// lane brings a row whose band is (wide), so the loop keeps one wave-uniform factor.
+__device__ __forceinline__ float screen_band(bool wide) {
+    return __builtin_amdgcn_ballot_w64(wide) ? INFINITY : 0x1p-20f;
+}
 // Step 1: the screened, clamped quotient; need = the IEEE divide must decide (rare).
-__device__ __forceinline__ float qdq_screen(float x, const QParams& p, float rs, bool& need) {
+__device__ __forceinline__ float qdq_screen(float x, const QParams& p, float rs, float band, bool& need) {
     const float a = (x + p.negmn) * rs;
     const float t = fminf(fmaxf(a, p.qmin), p.qmax);
     const float d = __builtin_amdgcn_fractf(t) - 0.5f;   // v_fract: t - floor(t), exact for |t| < 2^24
-    need = !(fabsf(d) > fabsf(t) * 0x1p-20f);
+    need = !(fabsf(d) > fabsf(t) * band);
     return t;
 }
 // Step 2 (only where need): the reference's quotient, clamped.

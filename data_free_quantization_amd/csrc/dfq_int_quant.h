@@ -15,6 +15,7 @@ struct IgAParams {
     int off;       // ig_offset
     QParams q;     // fp32 A only
     float rs;      // fp32 A only: rcp(q.s), qdq_screen's
+    float band;    // fp32 A only: qdq_screen's band factor (screen_rcp)
 };
 
 // The parameters as fq_given_kernel builds them: the range from min_dev[0] / max_dev[0] (device
@@ -25,7 +26,7 @@ __device__ __forceinline__ IgAParams ig_quant_params(const float* min_dev, const
     if (max_dev) gmax = (double)((const DFQ_GLOBAL float*)max_dev)[0];
     IgAParams p;
     p.q = make_qparams((float)gmin, (float)gmax, x_bits, x_symmetric != 0, x_flags | DFQ_GIVEN_RANGE, gmin, gmax);
-    p.rs = __builtin_amdgcn_rcpf(p.q.s);
+    p.rs = screen_rcp(p.q.s, p.band);
     p.s = p.q.s;
     p.z = p.q.mn;
     p.has_z = true;
@@ -42,7 +43,7 @@ __device__ __forceinline__ uint32_t ig_codes4(const float* x, const IgAParams& p
     float t[4];
     bool need[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) t[e] = qdq_screen(x[e], p.q, p.rs, need[e]);
+    for (int e = 0; e < 4; ++e) t[e] = qdq_screen(x[e], p.q, p.rs, p.band, need[e]);
     if (__builtin_amdgcn_ballot_w64(need[0] | need[1] | need[2] | need[3])) {   // wave-uniform, rare
 #pragma unroll
         for (int e = 0; e < 4; ++e)

@@ -200,7 +200,9 @@ __device__ __forceinline__ void issue_task_load(const DevTask& task, float* data
 //  * the reciprocal screen as |t - rint(t)| >= 0.5 - qabs 2^-20 (qabs = the larger of
 //    |qmin|, |qmax| >= |t|): a superset of the elements within |t| 2^-20 of a
 //    rounding boundary, which are the only ones whose reciprocal quotient can round
-//    differently from the IEEE divide; those take the divide.
+//    differently from the IEEE divide; those take the divide.  band: the task's
+//    screen_band -- +inf where a row's 1 / s is not a normal float, and then thr is
+//    -inf and every element takes the divide.
 //  * clamps as v_med3 (no operand canonicalisation: fminf / fmaxf on values the
 //    compiler cannot prove canonical cost a v_max x, x each).
 // CB: 0 no codes, 1 int8 / uint8, 2 int16, 3 packed int4.  EM: 0 no error sums,
@@ -209,14 +211,14 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <bool CLIP, int CB, int EM, bool NT>
 __device__ __forceinline__ void quant_vec4(const DevTensor& T, int n, int64_t base, float* data, const float* ls,
                                            const float* lmn, const float* lrs, const QParams& pc, bool whole,
-                                           int eoff, int lane, float qmin, float qmax, bool sym) {
+                                           int eoff, int lane, float qmin, float qmax, bool sym, float band) {
     constexpr float kMagic = 12582912.0f;   // 1.5 * 2^23
     const int nj = n >> 2;
     float* dq = T.dst + base;
     const float clo = T.clip_lo, chi = T.clip_hi;
     // whole-row tasks: the element's row; pieces: their one parameter set, in slot 0
     const uint32_t magic = whole ? T.len_magic : 0u;
-    const float thr = 0.5f - fmaxf(-qmin, qmax) * 0x1p-20f;
+    const float thr = 0.5f - fmaxf(-qmin, qmax) * band;   // band = +inf (screen_band): every element takes the divide
     const f32x2 mg = {kMagic, kMagic};
     struct Q4 {   // one float4's state between the screen and the stores
         float4 x;
@@ -310,21 +312,21 @@ __device__ __forceinline__ void quant_vec4(const DevTensor& T, int n, int64_t ba
 template <bool CLIP, int CB, bool NT>
 __device__ __forceinline__ void quant_vec4_e(int em, const DevTensor& T, int n, int64_t base, float* data,
                                              const float* ls, const float* lmn, const float* lrs, const QParams& pc,
-                                             bool whole, int eoff, int lane, float qmin, float qmax, bool sym) {
-    if (em == 0) quant_vec4<CLIP, CB, 0, NT>(T, n, base, data, ls, lmn, lrs, pc, whole, eoff, lane, qmin, qmax, sym);
-    else if (em == 1) quant_vec4<CLIP, CB, 1, NT>(T, n, base, data, ls, lmn, lrs, pc, whole, eoff, lane, qmin, qmax, sym);
-    else quant_vec4<CLIP, CB, 2, NT>(T, n, base, data, ls, lmn, lrs, pc, whole, eoff, lane, qmin, qmax, sym);
+                                             bool whole, int eoff, int lane, float qmin, float qmax, bool sym, float band) {
+    if (em == 0) quant_vec4<CLIP, CB, 0, NT>(T, n, base, data, ls, lmn, lrs, pc, whole, eoff, lane, qmin, qmax, sym, band);
+    else if (em == 1) quant_vec4<CLIP, CB, 1, NT>(T, n, base, data, ls, lmn, lrs, pc, whole, eoff, lane, qmin, qmax, sym, band);
+    else quant_vec4<CLIP, CB, 2, NT>(T, n, base, data, ls, lmn, lrs, pc, whole, eoff, lane, qmin, qmax, sym, band);
 }
 
 template <bool CLIP, bool NT>
 __device__ __forceinline__ void quant_vec4_c(int cb, int em, const DevTensor& T, int n, int64_t base, float* data,
                                              const float* ls, const float* lmn, const float* lrs, const QParams& pc,
-                                             bool whole, int eoff, int lane, float qmin, float qmax, bool sym) {
+                                             bool whole, int eoff, int lane, float qmin, float qmax, bool sym, float band) {
     switch (cb) {
-        case 0: quant_vec4_e<CLIP, 0, NT>(em, T, n, base, data, ls, lmn, lrs, pc, whole, eoff, lane, qmin, qmax, sym); break;
-        case 1: quant_vec4_e<CLIP, 1, NT>(em, T, n, base, data, ls, lmn, lrs, pc, whole, eoff, lane, qmin, qmax, sym); break;
-        case 2: quant_vec4_e<CLIP, 2, NT>(em, T, n, base, data, ls, lmn, lrs, pc, whole, eoff, lane, qmin, qmax, sym); break;
-        default: quant_vec4_e<CLIP, 3, NT>(em, T, n, base, data, ls, lmn, lrs, pc, whole, eoff, lane, qmin, qmax, sym);
+        case 0: quant_vec4_e<CLIP, 0, NT>(em, T, n, base, data, ls, lmn, lrs, pc, whole, eoff, lane, qmin, qmax, sym, band); break;
+        case 1: quant_vec4_e<CLIP, 1, NT>(em, T, n, base, data, ls, lmn, lrs, pc, whole, eoff, lane, qmin, qmax, sym, band); break;
+        case 2: quant_vec4_e<CLIP, 2, NT>(em, T, n, base, data, ls, lmn, lrs, pc, whole, eoff, lane, qmin, qmax, sym, band); break;
+        default: quant_vec4_e<CLIP, 3, NT>(em, T, n, base, data, ls, lmn, lrs, pc, whole, eoff, lane, qmin, qmax, sym, band);
     }
 }
 
@@ -379,7 +381,7 @@ __device__ __forceinline__ void compute_task(const DevTensor& T, const DevTask& 
                                              float* lmn, const uint32_t* __restrict__ slot_min,
                                              const uint32_t* __restrict__ slot_max, int lane, float bmn = 0.f,
                                              float bmx = 0.f, int goff = -1, uint64_t* tlm = nullptr,
-                                             uint32_t abl = 0) {
+                                             uint32_t abl = 0, float gband = 0x1p-20f) {
     const int n = task.n;
     const bool sym = is_sym(T.mode);
     const int len = (int)T.row_len;
@@ -389,8 +391,9 @@ __device__ __forceinline__ void compute_task(const DevTensor& T, const DevTask& 
     const bool group = goff >= 0;
     const bool whole = task.nrows > 0 || group;
     const int eoff = group ? goff : 0;
+    float band = gband;   // the task's screen_band (wave-uniform)
     if (group) {
-        // parameters set by the caller
+        // parameters set by the caller, gband with them
     } else if (whole) {
         // G lanes per row (G * next_pow2(nrows) = 64): every row of the task is
         // reduced at once; shuffles stay inside a G-lane group and every group
@@ -400,6 +403,7 @@ __device__ __forceinline__ void compute_task(const DevTensor& T, const DevTask& 
         while (p2 < nrows && p2 < kWave) p2 <<= 1;
         const int G = kWave / p2;
         const int sub = lane / G, sl = lane % G;
+        bool wide = false;   // some row's band is not 2^-20
         for (int r0 = 0; r0 < nrows; r0 += p2) {
             const int r = r0 + sub;
             float vmin = INFINITY, vmax = -INFINITY;
@@ -439,13 +443,16 @@ __device__ __forceinline__ void compute_task(const DevTensor& T, const DevTask& 
                 const QParams p = make_qparams(vmin, vmax, T.bits, sym, T.flags, T.given_min, T.given_max);
                 ls[r] = p.s;
                 lmn[r] = p.mn;
-                lmn[MAXROWS + r] = __builtin_amdgcn_rcpf(p.s);   // the quantize loop's 1/s
+                float b;
+                lmn[MAXROWS + r] = screen_rcp(p.s, b);   // the quantize loop's 1/s
+                wide |= b > 1.f;
                 const int64_t row_g = task.row0 + r;
                 if (T.scale) st<false>(T.scale + row_g, p.s);
                 if (T.zero) st<false>(T.zero + row_g, p.mn);
             }
             if (tlm && r0 == 0) tlm[3] = wall_clock64();   // diagnostics: their parameters built
         }
+        band = screen_band(wide);
         wave_lds_sync();
     } else {
         float mn = bmn, mx = bmx;   // block-row piece: the workgroup's combined range
@@ -462,10 +469,11 @@ __device__ __forceinline__ void compute_task(const DevTensor& T, const DevTask& 
             if (T.scale) st<false>(T.scale + row_g, pc.s);
             if (T.zero) st<false>(T.zero + row_g, pc.mn);
         }
+        const float prs = screen_rcp(pc.s, band);   // wave-uniform
         if (VEC && lane == 0) {   // the fixed-form quantize loop reads parameters from slot 0
             ls[0] = pc.s;
             lmn[0] = pc.mn;
-            lmn[MAXROWS] = __builtin_amdgcn_rcpf(pc.s);
+            lmn[MAXROWS] = prs;
         }
         if (VEC) wave_lds_sync();
     }
@@ -501,7 +509,7 @@ __device__ __forceinline__ void compute_task(const DevTensor& T, const DevTask& 
             return yv;
         }
         bool need;
-        float t = qdq_screen(xv, p, __builtin_amdgcn_rcpf(p.s), need);
+        float t = qdq_screen(xv, p, screen_rs(p.s), band, need);
         if (__builtin_amdgcn_ballot_w64(need)) {   // wave-uniform, rare
             if (need) t = qdq_exact_t(xv, p);
         }
@@ -512,10 +520,10 @@ __device__ __forceinline__ void compute_task(const DevTensor& T, const DevTask& 
     // four elements sharing one row's parameters: one reciprocal, one ballot
     auto four = [&](const float4& xv, const QParams& p, float& q0, float& q1, float& q2, float& q3) -> float4 {
         if constexpr (!SCREEN) return make_float4(one(xv.x, p, q0), one(xv.y, p, q1), one(xv.z, p, q2), one(xv.w, p, q3));
-        const float rs = __builtin_amdgcn_rcpf(p.s);
+        const float rs = screen_rs(p.s);
         bool n0, n1, n2, n3;
-        float t0 = qdq_screen(xv.x, p, rs, n0), t1 = qdq_screen(xv.y, p, rs, n1);
-        float t2 = qdq_screen(xv.z, p, rs, n2), t3 = qdq_screen(xv.w, p, rs, n3);
+        float t0 = qdq_screen(xv.x, p, rs, band, n0), t1 = qdq_screen(xv.y, p, rs, band, n1);
+        float t2 = qdq_screen(xv.z, p, rs, band, n2), t3 = qdq_screen(xv.w, p, rs, band, n3);
         if (__builtin_amdgcn_ballot_w64(n0 | n1 | n2 | n3)) {   // wave-uniform, rare
             if (n0) t0 = qdq_exact_t(xv.x, p);
             if (n1) t1 = qdq_exact_t(xv.y, p);
@@ -597,8 +605,8 @@ __device__ __forceinline__ void compute_task(const DevTensor& T, const DevTask& 
             if (T.dst && (!clip || T.clip_lo <= T.clip_hi)) {   // one compile-time body per (clip, codes, E form)
                 const int cb = !T.codes ? 0 : (T.code_bytes == 1 ? 1 : (T.code_bytes == 0 ? 3 : 2));
                 const int em = !want_e ? 0 : (khw == 1 ? 1 : 2);
-                if (clip) quant_vec4_c<true, NT>(cb, em, T, n, base, data, ls, lmn, lrs, pc, whole, eoff, lane, qmin, qmax, sym);
-                else quant_vec4_c<false, NT>(cb, em, T, n, base, data, ls, lmn, lrs, pc, whole, eoff, lane, qmin, qmax, sym);
+                if (clip) quant_vec4_c<true, NT>(cb, em, T, n, base, data, ls, lmn, lrs, pc, whole, eoff, lane, qmin, qmax, sym, band);
+                else quant_vec4_c<false, NT>(cb, em, T, n, base, data, ls, lmn, lrs, pc, whole, eoff, lane, qmin, qmax, sym, band);
                 done = true;
             }
         }
@@ -705,6 +713,7 @@ __device__ __forceinline__ bool compute_task_split(const DevTensor& T, const Dev
         while (p2 < nr && p2 < kWave) p2 <<= 1;
         const int G = kWave / p2;
         const int sub = lane / G, sl = lane % G;
+        bool wide = false;   // some row's band is not 2^-20
         for (int r0 = ra; r0 < rb; r0 += p2) {
             const int r = r0 + sub;
             float vmin = INFINITY, vmax = -INFINITY;
@@ -727,19 +736,22 @@ __device__ __forceinline__ bool compute_task_split(const DevTensor& T, const Dev
                 const QParams p = make_qparams(vmin, vmax, T.bits, sym, T.flags, T.given_min, T.given_max);
                 ls[r] = p.s;
                 lmn[r] = p.mn;
-                lmn[MAXROWS + r] = __builtin_amdgcn_rcpf(p.s);
+                float b;
+                lmn[MAXROWS + r] = screen_rcp(p.s, b);
+                wide |= b > 1.f;
                 const int64_t row_g = task.row0 + r;
                 if (T.scale) st<false>(T.scale + row_g, p.s);
                 if (T.zero) st<false>(T.zero + row_g, p.mn);
             }
         }
+        const float band = screen_band(wide);
         wave_lds_sync();
         // quantize rows [ra, rb): the fixed-form loop on that element span
         const int e0 = ra * len, ne = (rb - ra) * len;
         if (clip) quant_vec4_c<true, NT>(cb, em, T, ne, base + e0, data + e0, ls, lmn, lrs, pc, true, e0, lane, qmin,
-                                         qmax, sym);
+                                         qmax, sym, band);
         else quant_vec4_c<false, NT>(cb, em, T, ne, base + e0, data + e0, ls, lmn, lrs, pc, true, e0, lane, qmin, qmax,
-                                     sym);
+                                     sym, band);
     };
     vm_wait_le(M - m1);   // rows [0, h) have landed
     wave_lds_sync();
@@ -816,7 +828,7 @@ sweep_main_kernel(const DevTensor* __restrict__ tensors, const DevTask* __restri
                     continue;
                 }
             }
-            float bmn = 0.f, bmx = 0.f;
+            float bmn = 0.f, bmx = 0.f, gband = 0x1p-20f;
             int goff = -1;
             if (task.nrows <= kGroupTag) {
                 // row-group piece: the 4 waves of this block hold 4 pieces of R complete
@@ -865,18 +877,22 @@ sweep_main_kernel(const DevTensor* __restrict__ tensors, const DevTask* __restri
                     }
                 }
                 block_lds_sync();   // every wave has read the partials
+                bool wide = false;   // some row's band is not 2^-20
                 if (rr <= rl) {
                     const QParams p = make_qparams(gmn, gmx, T.bits, is_sym(T.mode), T.flags, T.given_min,
                                                    T.given_max);
                     ls[lane] = p.s;
                     lmn[lane] = p.mn;
-                    lmn[MAXROWS + lane] = __builtin_amdgcn_rcpf(p.s);
+                    float b;
+                    lmn[MAXROWS + lane] = screen_rcp(p.s, b);
+                    wide = b > 1.f;
                     if (rr * len >= g0) {   // the row starts in this piece: its parameters are stored once
                         const int64_t row_g = task.row0 + rr;
                         if (T.scale) st<false>(T.scale + row_g, p.s);
                         if (T.zero) st<false>(T.zero + row_g, p.mn);
                     }
                 }
+                gband = screen_band(wide);
                 wave_lds_sync();
                 goff = g0 - rf * len;
             } else if (task.nrows < 0) {   // block-row piece: all 4 waves of this block are here
@@ -918,10 +934,10 @@ sweep_main_kernel(const DevTensor* __restrict__ tensors, const DevTask* __restri
             uint64_t* tlm = TL ? marks : nullptr;
             if (T.vec4)
                 compute_task<MAXROWS, true, NT, ESPEC, SCREEN, FAST>(T, task, wl, ls, lmn, slot_min, slot_max, lane,
-                                                                     bmn, bmx, goff, tlm, abl);
+                                                                     bmn, bmx, goff, tlm, abl, gband);
             else
                 compute_task<MAXROWS, false, NT, ESPEC, SCREEN, FAST>(T, task, wl, ls, lmn, slot_min, slot_max, lane,
-                                                                      bmn, bmx, goff, tlm, abl);
+                                                                      bmn, bmx, goff, tlm, abl, gband);
             if constexpr (TL) {
                 if (lane == 0 && t < g_timeline_cap) {
                     uint32_t hw;

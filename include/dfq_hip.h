@@ -719,7 +719,10 @@ int dfq_int_gemm(const dfq_int_gemm_desc* d, void* stream);
  * always present).  Each lane quantizes the 16 elements its operand of the instruction
  * stands for; the codes of x never reach memory.  The result is bit for bit what
  * dfq_quantize_tensor (given range; codes, scale and zero of x) followed by dfq_int_gemm
- * gives.  Elements at k >= K and rows >= M are never read.  x 16-B aligned with ldx % 4 == 0
+ * gives.  A NaN element of x takes qmin's code -- fminf(fmaxf(NaN, qmin), qmax), this library's
+ * rule, not the reference's -- and the range may have any finite scale (above 2^126, where 1 / s
+ * is no normal float, every element takes the IEEE divide).  Elements at k >= K and rows >= M are
+ * never read.  x 16-B aligned with ldx % 4 == 0
  * and K % 4 == 0 takes 16-B loads, every other case 4-B loads with the same results.
  * Checks as dfq_int_gemm's, and DFQ_ERR_INVALID for a NULL x, x_bits outside 2..8,
  * x_symmetric not 0 / 1, x, min_dev or max_dev not 4-B aligned; DFQ_ERR_SHAPE for ldx < K. */

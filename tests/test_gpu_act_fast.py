@@ -94,3 +94,31 @@ def test_quantized_mobilenetv2_forward_fast_equals_generic():
         assert torch.isfinite(fast).all()
     finally:
         L.module_tensor_op = None
+
+
+@pytest.mark.parametrize("gmax,sym", [(2.2e40, True), (1.08e40, True), (1e40, True), (1e40, False)])
+def test_given_range_with_a_huge_scale_vs_oracle(gmax, sym):
+    """An 8-bit given range far beyond fp32 (the bounds are doubles): symmetric (-2.2e40, 2.2e40) has
+    a scale above 2^126, whose reciprocal is a subnormal float; (-1.08e40, 1.08e40) and
+    (-1e40, 1e40) lie just below.  Finite tie-dense data (tests/int_quant_edge_cases.boundary_x).
+    dfq_fake_quant_given divides (no reciprocal) and the generic path screens: both give the
+    oracle's dq bit for bit (infinities included) and NaN where it is NaN -- asymmetric, the zero
+    point is -inf and every dq is NaN -- and the generic path its codes, scale and zero."""
+    import numpy as np
+    from oracle import oracle as O
+    from tests import int_quant_edge_cases as E
+    from data_free_quantization_amd.utils.quantize import fake_quant, fake_quant_given
+    pair = (-gmax, gmax)
+    x = E.boundary_x((64, 168), pair, 8, sym) if sym else E.boundary_x((64, 168), (-3e38, 3e38), 8, False)
+    assert np.isfinite(x).all()
+    o = O.quantize(x, 8, O.TENSOR_SYM if sym else O.TENSOR_ASYM, rows=1, flags=O.F_GIVEN, given=pair)
+    nan = np.isnan(o["dq"])
+    assert nan.all() == (not sym) and nan.any() == (not sym) and len(np.unique(o["codes"])) >= (4 if sym else 1)
+    xd = torch.from_numpy(x).to(DEV)
+    r = fake_quant(xd, 8, symmetric=sym, min_value=pair[0], max_value=pair[1])
+    for dq in (fake_quant_given(xd, 8, sym, min_value=pair[0], max_value=pair[1]).cpu().numpy(), r.dq.cpu().numpy()):
+        assert np.array_equal(dq.view(np.int32)[~nan], o["dq"].view(np.int32)[~nan])
+        assert np.array_equal(np.isnan(dq), nan)
+    assert np.array_equal(r.codes.cpu().numpy(), o["codes"])
+    assert r.scale.cpu().numpy().view(np.int32)[0] == o["scale"].view(np.int32)[0]
+    assert r.zero.cpu().numpy().view(np.int32)[0] == o["zero"].view(np.int32)[0]

@@ -721,3 +721,42 @@ def test_signed_zeros_and_tiny_values_bitwise(mode, row_len, bits, clip):
     assert np.array_equal(it.zero.cpu().numpy().view(np.int32), o["zero"].view(np.int32))
     assert np.array_equal(it.esum.cpu().numpy().view(np.int32), o["esum"].view(np.int32))
     plan.destroy()
+
+
+#: 2-bit data ranges (lo, hi): the scale lies above 2^126, where 1 / s is a subnormal float, and the
+#: controls just below it (s = 8.5e37 < 2^126 = 8.507e37)
+_HUGE_SCALE_RANGES = {True: [(-1e38, 1e38), (-8.5e37, 8.5e37)], False: [(-2e38, 2.5e38), (-1.1e38, 1.45e38)]}
+
+
+@pytest.mark.parametrize("row_len", [576, 9])
+@pytest.mark.parametrize("control", [False, True], ids=["above_2p126", "below_2p126"])
+@pytest.mark.parametrize("mode", [0, 1, 2, 3])
+def test_scale_whose_reciprocal_is_subnormal_vs_oracle(mode, control, row_len):
+    """Rows of finite tie-dense values (tests/int_quant_edge_cases.boundary_x, every |x| <= FLT_MAX)
+    whose 2-bit scale lies above 2^126: 1 / s is a subnormal float, which the reciprocal
+    instruction may flush to zero -- then the screened quotient is 0 for every x and no element
+    takes the IEEE divide.  Symmetric with amax 1e38 and asymmetric on (-2e38, 2.5e38), per
+    channel and per tensor, the vector (576) and scalar (9) loops, next to a control whose scale is
+    just below 2^126: codes, dq, scale and zero bit for bit the oracle's."""
+    from data_free_quantization_amd.sweep import allocate, SweepPlan
+    from tests import int_quant_edge_cases as E
+    sym = mode in (1, 3)
+    lo, hi = (float(np.float32(t)) for t in _HUGE_SCALE_RANGES[sym][int(control)])
+    s, _ = E.qparams((lo, hi), 2, sym)
+    assert (float(s) > E.TWO_126) != control and float(s) > 0.99 * E.TWO_126
+    rows = 24
+    x = np.clip(E.boundary_x((rows, row_len), (lo, hi), 2, sym, seed=mode), np.float32(lo), np.float32(hi))
+    x[:, 0], x[:, 1] = lo, hi   # pin every row's range
+    assert np.isfinite(x).all()
+    t = torch.from_numpy(x).to(DEV)
+    it = allocate(t, bits=2, per_channel=mode >= 2, symmetric=sym, khw=1, want_esum=False)
+    plan = SweepPlan([it])
+    plan.execute()
+    torch.cuda.synchronize()
+    o = O.quantize(x, 2, mode, rows=rows)
+    assert float(o["scale"][0]) == float(s) and len(np.unique(o["codes"])) == (3 if sym else 4)   # -amax is code -1
+    assert np.array_equal(it.codes.cpu().numpy().view(o["codes"].dtype), o["codes"])
+    assert np.array_equal(it.dst.cpu().numpy().view(np.int32), o["dq"].view(np.int32))
+    assert np.array_equal(it.scale.cpu().numpy().view(np.int32), o["scale"].view(np.int32))
+    assert np.array_equal(it.zero.cpu().numpy().view(np.int32), o["zero"].view(np.int32))
+    plan.destroy()
