@@ -38,6 +38,7 @@ EXPORTS = [
     "dfq_act_moments", "dfq_act_minmax", "dfq_act_affine",
     "dfq_pair_stats_ws_bytes", "dfq_pair_stats_batch",
     "dfq_clip_search_ws_bytes", "dfq_clip_search_batch",
+    "dfq_sum_round_ws_bytes", "dfq_sum_round_batch",
     "dfq_mx_quantize_ws_bytes", "dfq_mx_quantize_batch", "dfq_mx_quantize_search_batch", "dfq_mx_gemm",
     "dfq_mx_linear", "dfq_mx_conv2d",
     "dfq_int_gemm", "dfq_int_linear", "dfq_int_conv2d", "dfq_int_dwconv2d",
@@ -109,6 +110,14 @@ class ClipSearchDesc(C.Structure):
         ("w", C.c_void_p), ("rows", C.c_int64), ("row_len", C.c_int64), ("bits", C.c_int32), ("mode", C.c_int32),
         ("candidates", C.c_int32), ("flags", C.c_int32), ("min_frac", C.c_float), ("reserved", C.c_int32),
         ("choice", C.c_void_p), ("range", C.c_void_p), ("noise", C.c_void_p), ("range_enc", C.c_void_p),
+    ]
+
+
+class SumRoundDesc(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("dst", C.c_void_p), ("codes", C.c_void_p), ("scale", C.c_void_p), ("zero", C.c_void_p),
+        ("flips", C.c_void_p), ("rows", C.c_int64), ("row_len", C.c_int64), ("khw", C.c_int32), ("bits", C.c_int32),
+        ("mode", C.c_int32), ("reserved", C.c_int32),
     ]
 
 
@@ -189,6 +198,7 @@ DFQ_BC_APPLY_VEC_SCRATCH = 1
 DFQ_BN_FOLD_ZERO_BIAS = 1
 DFQ_PAIR_PIECE_ELEMS = 8192
 DFQ_CLIP_PIECE_ELEMS, DFQ_CLIP_MAX_CANDIDATES, DFQ_CLIP_SEARCH_DRY = 4096, 64, 1
+DFQ_SR_MAX_ROW, DFQ_SR_MAX_KHW = 16384, 64
 DFQ_MX_BLOCK = 32
 DFQ_MX_FP4_E2M1, DFQ_MX_FP8_E4M3 = 0, 1
 DFQ_MX_FP6_E2M3, DFQ_MX_FP6_E3M2 = 0x23, 0x32   # self-describing (exponent, mantissa bits): 2 stays invalid
@@ -275,6 +285,8 @@ def load(path: Optional[os.PathLike] = None) -> C.CDLL:
         "dfq_pair_stats_batch": ([C.POINTER(PairDesc), I32, P, I64, P], C.c_int),
         "dfq_clip_search_ws_bytes": ([C.POINTER(ClipSearchDesc), I32], C.c_int64),
         "dfq_clip_search_batch": ([C.POINTER(ClipSearchDesc), I32, P, I64, P], C.c_int),
+        "dfq_sum_round_ws_bytes": ([C.POINTER(SumRoundDesc), I32], C.c_int64),
+        "dfq_sum_round_batch": ([C.POINTER(SumRoundDesc), I32, P, I64, P], C.c_int),
         "dfq_mx_quantize_ws_bytes": ([C.POINTER(MxDesc), I32], C.c_int64),
         "dfq_mx_quantize_batch": ([C.POINTER(MxDesc), I32, P, I64, P], C.c_int),
         "dfq_mx_quantize_search_batch": ([C.POINTER(MxDesc), I32, P, I64, P], C.c_int),

@@ -24,7 +24,8 @@ SOURCES = ["dfq_lib.hip", "dfq_sweep.hip", "dfq_sweep_plan.cpp", "dfq_transform.
            "dfq_cle_plan.cpp", "dfq_stats.hip", "dfq_stats_plan.cpp", "dfq_clip.hip", "dfq_clip_plan.cpp", "dfq_mx.hip", "dfq_mx_plan.cpp",
            "dfq_mx_gemm.hip", "dfq_mx_gemm_plan.cpp", "dfq_mx_linear_plan.cpp", "dfq_mx_conv_plan.cpp",
            "dfq_int_gemm.hip", "dfq_int_gemm_plan.cpp", "dfq_int_conv_plan.cpp",
-           "dfq_int_dwconv.hip", "dfq_int_dwconv_plan.cpp"]
+           "dfq_int_dwconv.hip", "dfq_int_dwconv_plan.cpp",
+           "dfq_round.hip", "dfq_round_plan.cpp"]   # sum rounding and its planner
 # Diagnostics build (bench.py's ceiling probes, scripts/ A/B runs): the same
 # sources with -DDFQ_DIAGNOSTICS (the sweep's A/B variants and environment
 # switches) plus the probes (include/dfq_diag.h).  Never loaded by the product path.
@@ -44,6 +45,10 @@ FLAGS = [
     # (libdfq_hip.so and libdfq_diag.so loaded together must not interpose)
     "-fvisibility=hidden", "-fvisibility-inlines-hidden",
 ]
+# per-source additions: the rounding kernel's fp32 arithmetic (one quotient, one
+# product and one sum per element, each rounded once) stays on the scalar-per-lane
+# fp32 instructions, never the packed two-wide ones
+SOURCE_FLAGS = {"dfq_round.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 # the same without the offload: hipcc takes a .cpp for HIP unless told otherwise
 # (the planner's placement compares doubles: -ffp-contract=off here too)
 HOST_FLAGS = ["-x", "c++"] + [f for f in FLAGS if "offload-arch" not in f and "-fhip-" not in f]
@@ -72,7 +77,7 @@ def _build_one(out: Path, sources, defines, force: bool, verbose: bool) -> Path:
     objs, cmds = [], []
     for s in sources:
         obj = CSRC / f"{Path(s).stem}.{tag}.o"
-        cmds.append([hipcc(), *(HOST_FLAGS if s.endswith(".cpp") else FLAGS), *defines, "-I", str(ROOT / "include"), "-I", str(CSRC), "-c", str(CSRC / s),
+        cmds.append([hipcc(), *(HOST_FLAGS if s.endswith(".cpp") else FLAGS), *SOURCE_FLAGS.get(s, []), *defines, "-I", str(ROOT / "include"), "-I", str(CSRC), "-c", str(CSRC / s),
                      "-o", str(obj)])
         objs.append(str(obj))
     if verbose:

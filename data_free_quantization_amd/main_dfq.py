@@ -77,6 +77,13 @@ Same flags and stage order; the transforms run on the GPU.  Additive flags:
                        NCHW, so every Conv2d / Linear product of MobileNetV2 and DeepLab is an
                        integer one.  Other grouped convolutions stay on fp32.  Needs
                        --int_matmul_conv
+  --rounding {nearest,sum}   nearest (default): every weight element rounds to its nearest code.
+                       sum: sum rounding (rounding.sum_round, dfq_sum_round_batch): the same grid, and
+                       the few elements nearest a tie flipped so that the summed rounding error of every
+                       kernel and of every output channel stays within half a step.  Needs --quantize and
+                       --weight_format int; not with --bc_mode fused, --world_size > 1 or a row longer
+                       than 16384 elements.  --clip_search and --clip_weight (outside --bc_mode fused)
+                       combine with it: they clamp the weights before / after
 
 Example (README.md:137 of the reference):
   python -m data_free_quantization_amd.main_dfq --task cls --relu --equalize --absorption \
@@ -166,7 +173,22 @@ def get_argument(argv=None):
     p.add_argument("--mx_scale_search", action="store_true",
                    help="MX weights: per block, the better of the floor rule's scale and the next one up by "
                         "the block's own quantization noise")
+    p.add_argument("--rounding", default="nearest", choices=["nearest", "sum"],
+                   help="integer weights: round to nearest, or sum rounding -- nearest plus the few flips that "
+                        "bound every kernel's and every output channel's summed rounding error")
     args = p.parse_args(argv)
+    if args.rounding == "sum":   # what quantize_targ_layer(rounding="sum") refuses, with its messages
+        if not args.quantize:
+            p.error("--rounding sum needs --quantize")
+        if args.weight_format != "int":
+            p.error("rounding='sum' rounds on an integer grid: it does not apply to weight_format=%r"
+                    % args.weight_format)
+        if args.clip_weight and args.bc_mode == "fused":
+            p.error("rounding='sum' has no fused clamp: clamp first with clip_weight or search_clip")
+        if args.world_size > 1:
+            p.error("rounding='sum' is not sharded: shard=True does not apply")
+        if args.bc_mode == "fused":
+            p.error("rounding='sum' writes no error sums (esum): the fused bias-correction hand-off is out of scope")
     if args.mx_matmul is not None and args.weight_format == "int":
         p.error("--mx_matmul needs an MX --weight_format")
     if args.mx_matmul_fused and args.mx_matmul is None:
@@ -336,7 +358,8 @@ def main(argv=None):
                                     granularity=args.granularity, symmetric=args.symmetric, clip=fused_clip,
                                     state=state, shard=sharded, weight_ranges=fold_ranges,
                                     **({"weight_format": args.weight_format} if mx_fmt else {}),
-                                    **({"mx_scale_search": True} if args.mx_scale_search else {}))
+                                    **({"mx_scale_search": True} if args.mx_scale_search else {}),
+                                    **({"rounding": "sum"} if args.rounding == "sum" else {}))
         set_quant_minmax(graph, bottoms)   # main_dfq.py:217
     if args.clip_weight and not (args.quantize and args.bc_mode == "fused"):
         clip_weight(graph, range_clip=[-15, 15], targ_type=targ_layer)

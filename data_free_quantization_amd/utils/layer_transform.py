@@ -207,7 +207,7 @@ def _identity_forward(bn):
 def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, *, granularity="tensor",
                         symmetric=False, clip=None, state: Optional[Dict] = None, shard: bool = False,
                         group=None, weight_ranges: Optional[Dict] = None, weight_format: str = "int",
-                        mx_scale_search: bool = False):
+                        mx_scale_search: bool = False, rounding: str = "nearest"):
     """Fake-quantize every target layer's weight (and bias when bits_bias < 32) in
     place, all layers in one grouped launch.
 
@@ -243,8 +243,30 @@ def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, *, gr
     (``mx.mx_quantize(scale_search=True)``).  The layers are also marked
     ``layer.mx_scale_search`` -- ``mx_matmul_forward`` must re-quantize such a weight with the
     search to get its stored values back -- and ``state[k]["scale_search"]``
-    is True; with the option off there is neither mark nor key."""
+    is True; with the option off there is neither mark nor key.
+
+    ``rounding="sum"`` (integer ``weight_format`` only; default ``"nearest"``): the weights
+    take sum rounding (``rounding.sum_round``) -- the sweep's grid, and the
+    few flips that keep every kernel's and every output channel's summed rounding error
+    within half a step -- in one call for all layers; biases stay on the sweep.
+    ``state[k]`` then holds ``codes``, ``scale``, ``zero``, ``khw``, ``rounding`` ("sum")
+    and ``flips`` (int32 [rows, 2]: kernel-stage and channel-stage flips per row).  The
+    call writes no error sums, so the fused bias-correction hand-off is out of scope:
+    asking such an entry for ``esum`` raises ValueError, as do an MX ``weight_format``,
+    ``clip=`` (clamp first with ``clip_weight`` / ``search_clip``) and ``shard=True``."""
     from ..mx import is_mx
+    if rounding not in ("nearest", "sum"):
+        raise ValueError("rounding must be 'nearest' or 'sum', got %r" % (rounding,))
+    if rounding == "sum":
+        if is_mx(weight_format) or mx_scale_search:
+            raise ValueError("rounding='sum' rounds on an integer grid: it does not apply to weight_format=%r"
+                             % (weight_format,))
+        if clip is not None:
+            raise ValueError("rounding='sum' has no fused clamp: clamp first with clip_weight or search_clip")
+        if shard:
+            raise ValueError("rounding='sum' is not sharded: shard=True does not apply")
+        return _quantize_targ_layer_sum(graph, bit_weight, bits_bias, targ_type, granularity=granularity,
+                                        symmetric=symmetric, state=state)
     if is_mx(weight_format):
         return _quantize_targ_layer_mx(graph, bits_bias, targ_type, weight_format, clip=clip, state=state,
                                        shard=shard, weight_ranges=weight_ranges, scale_search=bool(mx_scale_search))
@@ -309,6 +331,56 @@ def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, *, gr
         wk = [k for k in keys if k is not None]
         for k, it, sp in zip(wk, wl, spans):
             state[k] = _StateEntry(codes, f32, sp, tuple(it.src.shape), it.khw, up)
+    return graph
+
+
+class _SumRoundState(dict):
+    """A layer's state entry under rounding="sum": no error sums are written."""
+
+    def __missing__(self, key):
+        if key == "esum":
+            raise ValueError("rounding='sum' writes no error sums (esum): the fused bias-correction hand-off "
+                             "is out of scope")
+        raise KeyError(key)
+
+
+def _quantize_targ_layer_sum(graph, bit_weight, bits_bias, targ_type, *, granularity, symmetric, state):
+    """quantize_targ_layer with rounding="sum" (see there)."""
+    from ..rounding import SumRoundItem, sum_round
+    if granularity not in ("tensor", "channel"):
+        raise ValueError("granularity must be 'tensor' or 'channel'")
+    _lib.weights_changed()
+    print("Quantizing Layer parameters")
+    if bits_bias == 32:
+        print("Skipping bias quantization (32 bits)")
+    assert targ_type is not None, "targ_type cannot be None!"
+    tt = tuple(targ_type)
+    items, keys, biases = [], [], []
+    for layer_idx, layer in graph.items():
+        if type(layer) not in tt:
+            continue
+        layer.__dict__.pop("weight_format", None)   # an earlier MX pass's marks
+        layer.__dict__.pop("mx_scale_search", None)
+        lp = layer._parameters
+        w = lp["weight"].detach()
+        items.append(SumRoundItem(src=w, dst=w, bits=bit_weight, per_channel=granularity == "channel",
+                                  symmetric=symmetric, khw=khw_of(w), want_codes=state is not None,
+                                  want_flips=state is not None))
+        keys.append(layer_idx)
+        if lp.get("bias") is not None and bits_bias < 32:
+            b = lp["bias"]
+            biases.append(SweepItem(src=b, dst=b, bits=bits_bias, per_channel=False, symmetric=False, rows=1))
+    if not items:
+        return graph
+    results = sum_round(items)
+    if biases:
+        plan = SweepPlan(biases)
+        plan.execute()
+        plan.destroy()
+    if state is not None:
+        for k, it, r in zip(keys, items, results):
+            state[k] = _SumRoundState(codes=r.codes, scale=r.scale, zero=r.zero, khw=it.khw, rounding="sum",
+                                      flips=r.flips)
     return graph
 
 

@@ -421,6 +421,65 @@ int64_t dfq_clip_search_ws_bytes(const dfq_clip_search_desc* descs, int32_t n);
  * weight at most once per call.  n == 0: DFQ_OK, nothing launched. */
 int dfq_clip_search_batch(const dfq_clip_search_desc* descs, int32_t n, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- sum rounding: nearest rounding with the few flips that bound every kernel's
+ *      and every output channel's summed rounding error (no reference counterpart;
+ *      weight-only adaptive rounding after SQuant, ICLR 2022) ---------------------
+ * The weight is viewed as [rows, row_len], row_len = G * T: G kernels of T = khw
+ * consecutive taps (T = 1 for Linear and 1x1).  The unit is the row in the CHANNEL
+ * modes and the tensor in the TENSOR modes.
+ *  1. p = make_qparams(mn, mx, bits, sym) on the unit's fp32 data range, as the sweep
+ *     forms it (scale in double); scale = p.s and zero = p.mn are the sweep's bits.
+ *  2. t_i = clamp(fl32(fl32(x_i + negmn) / s), qmin, qmax), the IEEE divide for every
+ *     element; q_i = rintf(t_i).
+ *  3. P_i = (int32) rintf(ldexpf(q_i - t_i, 24)): q_i - t_i is exact in fp32, |P_i| <=
+ *     2^23, a clamped element has P_i = 0.  Everything below is integer arithmetic with
+ *     exact sums, so no reduction order or block shape can change a bit.
+ *  4. Kernel stage, per kernel: e = sum of its P; k = (|e| + 2^23 - 1) >> 24 (round half
+ *     down: a lone exact tie stays).  e > 0: the k elements with the largest P among
+ *     those with P > 0 flip down (q -= 1, P -= 2^24); e < 0: the k with the smallest P
+ *     among P < 0 flip up.  Equal P: the lower tap index.  Then |e'| <= 2^23.
+ *  5. Channel stage, per row: E = sum of e'; k = (|E| + 2^23 - 1) >> 24.  E > 0: the k
+ *     kernels with the largest e' among e' > 0 (equal e': the lower g) each flip down
+ *     their not-yet-flipped element with the largest P > 0 (equal P: the lower tap);
+ *     E < 0 is the mirror image.  A chosen kernel without such an element -- its own
+ *     stage-4 flips went up and overshot, and every other P is <= 0 -- takes back one of
+ *     those flips instead: the flipped-up element with the largest P (equal P: the lower
+ *     tap) returns to its nearest code.  Then |E'| <= 2^23, every |e''| <= 2^24 + 2^23,
+ *     and every code is within one step of nearest.
+ *  6. codes = the final q (uint8 asymmetric, int8 symmetric); dst = fl(fl(q * s) + mn),
+ *     may alias src; flips[row] = {stage-4 flips, stage-5 flips} of the row.
+ * Candidates always exist and stay on the grid.  Non-finite weights
+ * are outside the contract.  No esum, fused clip, given range or range_enc: clamp
+ * first with dfq_clamp_batch / dfq_clip_search_batch, which work in place. */
+enum { DFQ_SR_MAX_ROW = 16384 };   /* a longer row_len: DFQ_ERR_UNSUPPORTED (a row's P lives in LDS) */
+enum { DFQ_SR_MAX_KHW = 64 };      /* a larger khw: DFQ_ERR_UNSUPPORTED (one lane owns a whole kernel) */
+typedef struct dfq_sum_round_desc {
+    const float* src;     /* 4-B aligned */
+    float*       dst;     /* fp32 dequantized values, or NULL */
+    void*        codes;   /* [rows * row_len] bytes, or NULL */
+    float*       scale;   /* [rows] (CHANNEL modes) or [1] (TENSOR modes), or NULL */
+    float*       zero;    /* as scale */
+    int32_t*     flips;   /* [rows][2], or NULL */
+    int64_t      rows;    /* >= 1 */
+    int64_t      row_len; /* 1..DFQ_SR_MAX_ROW, a multiple of khw (else DFQ_ERR_SHAPE) */
+    int32_t      khw;     /* 1..DFQ_SR_MAX_KHW */
+    int32_t      bits;    /* 2..8 */
+    int32_t      mode;    /* DFQ_TENSOR_ASYM ... DFQ_CHANNEL_SYM */
+    int32_t      reserved;
+} dfq_sum_round_desc;
+/* Device workspace bytes for dfq_sum_round_batch (-1: a descriptor it would refuse). */
+int64_t dfq_sum_round_ws_bytes(const dfq_sum_round_desc* descs, int32_t n);
+/* Asynchronous on `stream`, no host wait (the table goes up through the library's
+ * pinned staging ring): one launch, preceded by one range launch when a weight is in
+ * a TENSOR mode.  ws as for dfq_clip_search_batch.  DFQ_ERR_INVALID for a bad
+ * descriptor (NULL or misaligned src, every output NULL, rows or row_len < 1, bits
+ * outside 2..8, mode, khw < 1, non-zero reserved, more than 65535 weights) or a
+ * misaligned ws, DFQ_ERR_SHAPE for row_len % khw != 0, DFQ_ERR_UNSUPPORTED beyond
+ * DFQ_SR_MAX_ROW / DFQ_SR_MAX_KHW, DFQ_ERR_WORKSPACE for a NULL or small ws.  Each
+ * weight at most once per call; a weight's results are the same bits whatever the
+ * rest of the list or its order.  n == 0: DFQ_OK, nothing launched. */
+int dfq_sum_round_batch(const dfq_sum_round_desc* descs, int32_t n, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- OCP Microscaling (MX) block-scaled weight quantization (no reference
  *      counterpart; the operand format of CDNA4's scaled matrix instructions) ----
  * Every row of the [rows, row_len] view is cut into blocks of DFQ_MX_BLOCK = 32
