@@ -42,6 +42,7 @@ EXPORTS = [
     "dfq_mx_quantize_ws_bytes", "dfq_mx_quantize_batch", "dfq_mx_quantize_search_batch", "dfq_mx_gemm",
     "dfq_mx_linear", "dfq_mx_conv2d",
     "dfq_int_gemm", "dfq_int_linear", "dfq_int_conv2d", "dfq_int_dwconv2d",
+    "dfq_int_gemm_grouped", "dfq_int_linear_grouped", "dfq_int_conv2d_grouped",
 ]
 #: entry points only the diagnostics library exports (include/dfq_diag.h)
 DIAG_EXPORTS = ["dfq_probe_stream", "dfq_probe_lds", "dfq_debug_timeline", "dfq_debug_ablate",
@@ -297,6 +298,9 @@ def load(path: Optional[os.PathLike] = None) -> C.CDLL:
         "dfq_int_linear": ([C.POINTER(IntLinearDesc), P], C.c_int),
         "dfq_int_conv2d": ([C.POINTER(IntConv2dDesc), P], C.c_int),
         "dfq_int_dwconv2d": ([C.POINTER(IntDwConv2dDesc), P], C.c_int),
+        "dfq_int_gemm_grouped": ([C.POINTER(IntGemmDesc), C.c_int32, P], C.c_int),
+        "dfq_int_linear_grouped": ([C.POINTER(IntLinearDesc), C.c_int32, P], C.c_int),
+        "dfq_int_conv2d_grouped": ([C.POINTER(IntConv2dDesc), C.c_int32, P], C.c_int),
     }
     diag = {
         "dfq_probe_stream": ([P, P, P, P, I64, I32, P], C.c_int),

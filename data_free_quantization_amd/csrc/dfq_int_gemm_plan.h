@@ -107,4 +107,32 @@ inline int ig_check_common(const Desc& d, bool a_ok, int64_t lda, int32_t known_
 int ig_check(const dfq_int_gemm_desc* d, int64_t& grid);
 int igl_check(const dfq_int_linear_desc* d, int64_t& grid);
 
+// ---- group-wise B parameters (dfq_int_*_grouped; dfq_int_group.hip) ----
+// b_scale / b_zero hold [N][G] values, G = ceil(K / g); group j covers k in [j g, min((j + 1) g, K)).
+// g is a multiple of the K step -- a group closes between two steps -- or half a step: ig_lane_k0
+// puts k = 64 s + 16 (lane >> 4) in a lane, so lanes 0..31 hold the step's first group and lanes
+// 32..63 its second, and the step runs as two passes, each with the other half's A operand zero.
+constexpr int kIggHalf = kIgStepK / 2;
+DFQ_HOST_DEVICE inline bool igg_allowed(int64_t g) { return g == kIggHalf || (g >= kIgStepK && g <= kIgMaxK && g % kIgStepK == 0); }
+DFQ_HOST_DEVICE inline int64_t igg_groups(int64_t K, int64_t g) { return ceil_div(K, g); }
+DFQ_HOST_DEVICE inline int igg_passes(int g) { return g == kIggHalf ? 2 : 1; }
+// The group that pass `pass` of K step `step` adds to, and whether that pass is the group's last.
+DFQ_HOST_DEVICE inline int igg_group(int step, int pass, int g) { return g == kIggHalf ? 2 * step + pass : step / (g / kIgStepK); }
+DFQ_HOST_DEVICE inline bool igg_closes(int step, int steps, int g) {
+    return g == kIggHalf || step + 1 == steps || (step + 1) % (g / kIgStepK) == 0;
+}
+// The lane's elements of the step belong to the pass.
+DFQ_HOST_DEVICE inline bool igg_lane_in_pass(int lane, int pass, int g) { return g != kIggHalf || (lane >> 5) == pass; }
+// The contract's K_j: elements of group j (the last may be short); <= 0: there is no group j.
+DFQ_HOST_DEVICE inline int igg_group_len(int j, int g, int64_t K) {
+    const int64_t left = K - (int64_t)j * g;
+    return left < g ? (int)left : g;
+}
+DFQ_HOST_DEVICE inline int64_t igg_param_offset(int64_t n, int64_t j, int64_t G) { return n * G + j; }
+// The grouped entries' own checks, after the old entries': b_group and the flag it excludes.
+inline int igg_check(int32_t b_group, int32_t flags) {
+    if (b_group < 1 || (flags & DFQ_INT_B_PER_ROW)) return DFQ_ERR_INVALID;
+    return igg_allowed(b_group) ? DFQ_OK : DFQ_ERR_UNSUPPORTED;
+}
+
 }  // namespace dfq

@@ -9,8 +9,10 @@ the im2col rows of an NCHW input, gathered inside the kernel, with zero padding 
 the real value 0; ``int_dwconv2d`` is the depthwise convolution (groups == C) on the packed
 8-bit dot instruction, each input element quantized once.  The integer sums are exact
 and the affine terms are applied in fp64 in a fixed order, so every output is bit for bit a
-numpy float64 statement (tests/int_gemm_cases.py).  There is no CPU fallback: CPU tensors
-raise."""
+numpy float64 statement (tests/int_gemm_cases.py).  ``b_group`` (``int_gemm``, ``int_linear``)
+and ``int_conv2d_grouped`` take group-wise weight parameters, a scale and zero per 32, 64, 128, ...
+elements of a weight row (``group_quant`` writes them; tests/int_group_cases.py).  There is no CPU
+fallback: CPU tensors raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -69,9 +71,32 @@ def _k_arg(K) -> int:
     return K
 
 
-def _b_args(d, b_codes, b_scale, b_zero, K: int, b_packed: bool) -> int:
-    """B's checks and descriptor fields (shared by the two descriptors); N."""
+def group_allowed(b_group: int) -> bool:
+    """The group sizes the kernels take: 32 (half a K step), or a multiple of 64 up to MAX_K."""
+    return b_group == 32 or (64 <= b_group <= MAX_K and b_group % 64 == 0)
+
+
+def _group_arg(b_group) -> Optional[int]:
+    if b_group is None:
+        return None
+    b_group = int(b_group)
+    if not group_allowed(b_group):
+        raise ValueError("b_group must be 32 or a multiple of 64 up to %d, got %d" % (MAX_K, b_group))
+    return b_group
+
+
+def _b_args(d, b_codes, b_scale, b_zero, K: int, b_packed: bool, b_group: Optional[int] = None) -> int:
+    """B's checks and descriptor fields (shared by the descriptors); N.  ``b_group``: the
+    parameters are [N, ceil(K / b_group)] and DFQ_INT_B_PER_ROW stays clear."""
     N = _codes_arg("b_codes", b_codes, K, b_packed)
+    if b_group is not None:
+        _param_arg("b_scale", b_scale, (N * -(-K // b_group),))
+        _param_arg("b_zero", b_zero, (b_scale.numel(),), optional=True)
+        d.b_codes, d.b_scale = b_codes.data_ptr(), b_scale.data_ptr()
+        d.b_zero = b_zero.data_ptr() if b_zero is not None else None
+        d.b_signed = int(b_codes.dtype == torch.int8)
+        d.flags |= _lib.DFQ_INT_B_PACK4 if b_packed else 0
+        return N
     _param_arg("b_scale", b_scale, (1, N) if N > 1 else (1,))
     _param_arg("b_zero", b_zero, (b_scale.numel(),), optional=True)
     d.b_codes, d.b_scale = b_codes.data_ptr(), b_scale.data_ptr()
@@ -96,6 +121,17 @@ def _range_args(d, min_dev, max_dev, min_value, max_value, scale_f32: bool) -> N
     d.flags = _lib.DFQ_SCALE_F32 if scale_f32 else 0
 
 
+def _launch(name: str, d, b_group: Optional[int], dev) -> None:
+    """The entry point ``name``, or its ``_grouped`` form under a group size."""
+    L = _lib.load()
+    if b_group is None:
+        rc = getattr(L, name)(C.byref(d), _lib.raw_stream(dev))
+    else:
+        name += "_grouped"
+        rc = getattr(L, name)(C.byref(d), b_group, _lib.raw_stream(dev))
+    _lib.check(rc, name, ValueError)
+
+
 def _bias_out_args(what: str, d, M: int, N: int, K: int, dev, bias, out, others) -> torch.Tensor:
     """mx.py's checks of ``bias``, ``out`` and the tensors' device; the descriptor fields both entries share."""
     out = mx._bias_out_args(what, M, N, dev, bias, out, others)
@@ -107,7 +143,8 @@ def _bias_out_args(what: str, d, M: int, N: int, K: int, dev, bias, out, others)
 
 def int_gemm(a_codes: torch.Tensor, a_scale: torch.Tensor, a_zero: Optional[torch.Tensor], b_codes: torch.Tensor,
              b_scale: torch.Tensor, b_zero: Optional[torch.Tensor], K: int, *, b_packed: bool = False,
-             bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+             bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+             b_group: Optional[int] = None) -> torch.Tensor:
     """out[m, n] = sum_k (qa[m, k] * sa + za) * (qb[n, k] * sb[n] + zb[n]) (+ bias[n]) on the
     i8 matrix instruction (dfq_int_gemm).  ``a_codes``: M * K bytes, ``b_codes``:
     N * K bytes -- or N * K / 2 packed bytes with ``b_packed`` (the sweep's ``pack_int4`` layout,
@@ -116,19 +153,26 @@ def int_gemm(a_codes: torch.Tensor, a_scale: torch.Tensor, a_zero: Optional[torc
     symmetric codes as int8).  ``a_scale`` / ``a_zero``: one fp32 value each; ``b_scale`` /
     ``b_zero``: one value each, or N (per output channel); a zero may be None (0).  ``out``:
     fp32 [M, N] whose rows may be strided; allocated when None.  The result is the contract's
-    fp64 statement bit for bit.  One launch, asynchronous on the current stream."""
+    fp64 statement bit for bit.  One launch, asynchronous on the current stream.
+
+    ``b_group`` (32, or a multiple of 64): group-wise B -- ``b_scale`` / ``b_zero`` hold
+    [N, ceil(K / b_group)] values, one per ``b_group`` consecutive elements of a row (the last
+    group may be short; ``group_quant`` writes them), and the result is the grouped statement
+    (dfq_int_gemm_grouped): the groups' fp64 terms in ascending order.  One group (b_group >= K)
+    gives the per-row call's bits.  A disallowed size or a wrong count raises ValueError."""
     K = _k_arg(K)
+    b_group = _group_arg(b_group)
     M = _codes_arg("a_codes", a_codes, K)
     _param_arg("a_scale", a_scale, (1,))
     _param_arg("a_zero", a_zero, (1,), optional=True)
     d = _lib.IntGemmDesc()
-    N = _b_args(d, b_codes, b_scale, b_zero, K, bool(b_packed))
+    N = _b_args(d, b_codes, b_scale, b_zero, K, bool(b_packed), b_group)
     dev = a_codes.device
     out = _bias_out_args("int_gemm", d, M, N, K, dev, bias, out, (a_scale, a_zero, b_codes, b_scale, b_zero))
     d.a_codes, d.a_scale = a_codes.data_ptr(), a_scale.data_ptr()
     d.a_zero = a_zero.data_ptr() if a_zero is not None else None
     d.a_signed = int(a_codes.dtype == torch.int8)
-    _lib.check(_lib.load().dfq_int_gemm(C.byref(d), _lib.raw_stream(dev)), "dfq_int_gemm", ValueError)
+    _launch("dfq_int_gemm", d, b_group, dev)
     return out
 
 
@@ -145,16 +189,18 @@ def int_linear(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor, b_
                bits: int = 8, symmetric: bool = False, min_dev: Optional[torch.Tensor] = None,
                max_dev: Optional[torch.Tensor] = None, min_value=None, max_value=None, scale_f32: bool = False,
                b_packed: bool = False, bias: Optional[torch.Tensor] = None,
-               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+               out: Optional[torch.Tensor] = None, b_group: Optional[int] = None) -> torch.Tensor:
     """``int_gemm`` with A given as fp32 ``x`` [M, K] and quantized to ``bits`` (2..8) inside the
     kernel (dfq_int_linear): the quantizer is ``fake_quant_given``'s -- the range from the
     device scalars ``min_dev`` / ``max_dev`` (no host synchronisation) or the Python floats
     ``min_value`` / ``max_value``, ``scale_f32`` as there -- and the codes of x never reach
     memory.  Bit for bit ``fake_quant`` of x on that range (codes, scale, zero) followed by
     ``int_gemm``.  ``x`` needs unit column stride; any row stride >= K is passed on (a column
-    slice of a wider tensor is read in place).  B, ``bias`` and ``out`` as for ``int_gemm``."""
+    slice of a wider tensor is read in place).  B, ``bias``, ``out`` and ``b_group`` as for
+    ``int_gemm``."""
     global LINEAR_CALLS
     K = _k_arg(K)
+    b_group = _group_arg(b_group)
     bits = int(bits)
     if not 2 <= bits <= 8:
         raise ValueError("bits must be 2..8, got %d" % bits)
@@ -166,12 +212,12 @@ def int_linear(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor, b_
                          % (K, K, tuple(x.shape), tuple(x.stride())))
     d = _lib.IntLinearDesc()
     _range_args(d, min_dev, max_dev, min_value, max_value, scale_f32)
-    N = _b_args(d, b_codes, b_scale, b_zero, K, bool(b_packed))
+    N = _b_args(d, b_codes, b_scale, b_zero, K, bool(b_packed), b_group)
     M, dev = x.shape[0], x.device
     out = _bias_out_args("int_linear", d, M, N, K, dev, bias, out, (min_dev, max_dev, b_codes, b_scale, b_zero))
     d.x, d.ldx = x.data_ptr(), (x.stride(0) if M > 1 else max(x.stride(0), K))
     d.x_bits, d.x_symmetric = bits, int(bool(symmetric))
-    _lib.check(_lib.load().dfq_int_linear(C.byref(d), _lib.raw_stream(dev)), "dfq_int_linear", ValueError)
+    _launch("dfq_int_linear", d, b_group, dev)
     LINEAR_CALLS += 1
     return out
 
@@ -192,6 +238,28 @@ def int_conv2d(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor, b_
     on that matrix, reshaped to NCHW.  ``kernel_size``, ``stride``, ``padding``, ``dilation``: ints
     or (h, w) pairs.  ``out``: fp32 contiguous [B, N, OH, OW]; allocated when None.  Counts in
     ``LINEAR_CALLS``.  Asynchronous on the current stream."""
+    return _conv2d(x, b_codes, b_scale, b_zero, kernel_size, stride, padding, dilation, None, bits, symmetric, min_dev, max_dev,
+                   min_value, max_value, scale_f32, b_packed, bias, out)
+
+
+def int_conv2d_grouped(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor, b_zero: Optional[torch.Tensor], kernel_size,
+                       stride=1, padding=0, dilation=1, *, b_group: int, bits: int = 8, symmetric: bool = False,
+                       min_dev: Optional[torch.Tensor] = None, max_dev: Optional[torch.Tensor] = None, min_value=None,
+                       max_value=None, scale_f32: bool = False, b_packed: bool = False,
+                       bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``int_conv2d`` with group-wise B (dfq_int_conv2d_grouped): ``b_group`` as for ``int_gemm``,
+    ``b_scale`` / ``b_zero`` [N, ceil(K / b_group)], the groups running along (c, kh, kw), the
+    order the weight is stored in; a group's constant term counts its taps inside the image.
+    (Its own function: ``int_conv2d`` and ``int_dwconv2d`` keep one signature.)"""
+    if b_group is None:
+        raise ValueError("b_group must be 32 or a multiple of 64")
+    return _conv2d(x, b_codes, b_scale, b_zero, kernel_size, stride, padding, dilation, _group_arg(b_group), bits, symmetric,
+                   min_dev, max_dev, min_value, max_value, scale_f32, b_packed, bias, out)
+
+
+def _conv2d(x, b_codes, b_scale, b_zero, kernel_size, stride, padding, dilation, b_group, bits, symmetric, min_dev, max_dev,
+            min_value, max_value, scale_f32, b_packed, bias, out) -> torch.Tensor:
+    """int_conv2d's and int_conv2d_grouped's checks and launch."""
     global LINEAR_CALLS
     bits = int(bits)
     if not 2 <= bits <= 8:
@@ -209,7 +277,7 @@ def int_conv2d(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor, b_
     K = _k_arg(Cin * KH * KW)
     d = _lib.IntConv2dDesc()
     _range_args(d, min_dev, max_dev, min_value, max_value, scale_f32)
-    N = _b_args(d, b_codes, b_scale, b_zero, K, bool(b_packed))
+    N = _b_args(d, b_codes, b_scale, b_zero, K, bool(b_packed), b_group)
     OH, OW = mx.conv_out_size(H, KH, sh, ph, dh), mx.conv_out_size(W, KW, sw, pw, dw)
     if OH < 1 or OW < 1:
         raise ValueError("the kernel %s (dilation %s) does not fit the padded input %s" % ((KH, KW), (dh, dw), (H + 2 * ph, W + 2 * pw)))
@@ -233,7 +301,7 @@ def int_conv2d(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor, b_
     d.B, d.C, d.H, d.W, d.N, d.KH, d.KW = B, Cin, H, W, N, KH, KW
     d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w = sh, sw, ph, pw, dh, dw
     d.x_bits, d.x_symmetric = bits, int(bool(symmetric))
-    _lib.check(_lib.load().dfq_int_conv2d(C.byref(d), _lib.raw_stream(dev)), "dfq_int_conv2d", ValueError)
+    _launch("dfq_int_conv2d", d, b_group, dev)
     LINEAR_CALLS += 1
     return out
 
@@ -303,3 +371,36 @@ def int_dwconv2d(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor, 
     _lib.check(_lib.load().dfq_int_dwconv2d(C.byref(d), _lib.raw_stream(dev)), "dfq_int_dwconv2d", ValueError)
     LINEAR_CALLS += 1
     return out
+
+
+def group_quant(w2d: torch.Tensor, bits: int, group: int, *, symmetric: bool = False, packed: bool = False):
+    """Group-wise codes of a weight for ``int_gemm(b_group=group)``: (codes [N, K] -- or packed
+    [N, K / 2] nibbles, int8 when symmetric -- scale [N, G], zero [N, G]), G = ceil(K / group).
+    The sweep's per-channel mode on the [N * K / group, group] view of ``w2d`` [N, K]; a ragged
+    K is the body ``w2d[:, :K - K % group]`` swept that way and the tail ``w2d[:, K - K % group:]``
+    swept per row, joined column-wise.  No arithmetic of its own."""
+    from . import sweep
+    from .utils.quantize import fake_quant
+    group = _group_arg(group)
+    if group is None or w2d.dim() != 2 or w2d.numel() == 0:
+        raise ValueError("group_quant takes a non-empty [N, K] weight and a group size")
+    N, K = w2d.shape
+    if packed and (bits > 4 or K % 2):
+        raise ValueError("packed codes need bits <= 4 and an even K")
+
+    def rows_of(part: torch.Tensor, row_len: int):
+        view = part.contiguous().reshape(-1, row_len)
+        if not packed:
+            r = fake_quant(view, bits, per_channel=True, symmetric=symmetric)
+            return r.codes.reshape(N, -1), r.scale.reshape(N, -1), r.zero.reshape(N, -1)
+        it = sweep.allocate(view, bits=bits, per_channel=True, symmetric=symmetric, pack_int4=True)
+        plan = sweep.SweepPlan([it])
+        plan.execute()
+        plan.destroy()
+        codes = it.codes.view(torch.int8) if symmetric else it.codes
+        return codes.reshape(N, -1), it.scale.reshape(N, -1), it.zero.reshape(N, -1)
+
+    body = K - K % group
+    parts = ([rows_of(w2d[:, :body], group)] if body else []) + ([rows_of(w2d[:, body:], K - body)] if K > body else [])
+    codes, scale, zero = (torch.cat([p[i] for p in parts], dim=1).contiguous() for i in range(3))
+    return codes, scale, zero

@@ -132,7 +132,10 @@ def get_argument(argv=None):
     p.add_argument("--model", default=None, choices=list(zoo.MODELS))
     p.add_argument("--weights", default=None)
     p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--granularity", default="tensor", choices=["tensor", "channel"])
+    p.add_argument("--granularity", default="tensor", choices=["tensor", "channel", "group"])
+    p.add_argument("--group_size", type=int, default=None,
+                   help="with --granularity group: an fp32 scale and zero per this many consecutive elements of a weight "
+                        "row; a layer whose row length is no multiple of it falls back to per channel")
     p.add_argument("--symmetric", action="store_true")
     p.add_argument("--bc_mode", default="literal", choices=["literal", "reference", "fused"])
     p.add_argument("--val", default="./val")
@@ -189,6 +192,18 @@ def get_argument(argv=None):
             p.error("rounding='sum' is not sharded: shard=True does not apply")
         if args.bc_mode == "fused":
             p.error("rounding='sum' writes no error sums (esum): the fused bias-correction hand-off is out of scope")
+    if (args.granularity == "group") != (args.group_size is not None):
+        p.error("--granularity group and --group_size go together")
+    if args.granularity == "group":   # what quantize_targ_layer(granularity="group") refuses
+        if not args.quantize or args.group_size < 1:
+            p.error("--granularity group needs --quantize and --group_size >= 1")
+        for flag, on in (("--rounding sum", args.rounding == "sum"), ("--world_size > 1", args.world_size > 1),
+                         ("--clip_search", args.clip_search), ("an MX --weight_format", args.weight_format != "int"),
+                         ("--bc_mode fused (a group-wise sweep writes no error sums)", args.bc_mode == "fused"),
+                         ("--export (its writer takes one parameter per tensor or per row)", bool(args.export)),
+                         ("--int_matmul (the forward scope re-quantizes every weight per tensor)", args.int_matmul)):
+            if on:
+                p.error("--granularity group does not apply to %s" % flag)
     if args.mx_matmul is not None and args.weight_format == "int":
         p.error("--mx_matmul needs an MX --weight_format")
     if args.mx_matmul_fused and args.mx_matmul is None:
@@ -359,7 +374,8 @@ def main(argv=None):
                                     state=state, shard=sharded, weight_ranges=fold_ranges,
                                     **({"weight_format": args.weight_format} if mx_fmt else {}),
                                     **({"mx_scale_search": True} if args.mx_scale_search else {}),
-                                    **({"rounding": "sum"} if args.rounding == "sum" else {}))
+                                    **({"rounding": "sum"} if args.rounding == "sum" else {}),
+                                    **({"group_size": args.group_size} if args.granularity == "group" else {}))
         set_quant_minmax(graph, bottoms)   # main_dfq.py:217
     if args.clip_weight and not (args.quantize and args.bc_mode == "fused"):
         clip_weight(graph, range_clip=[-15, 15], targ_type=targ_layer)
@@ -391,7 +407,10 @@ def main(argv=None):
                if args.clip_search else {}),
             **({"weight_format": args.weight_format, "bits_per_weight": mx.bits_per_weight(args.weight_format)}
                if args.weight_format != "int" else {}),
-            **({"mx_scale_search": True} if args.mx_scale_search else {})}, clip_search=searched,
+            **({"mx_scale_search": True} if args.mx_scale_search else {}),
+            **({"group_size": args.group_size, "per_channel_fallback_layers": sum(
+                1 for l in graph.values() if type(l) in tuple(targ_layer) and l.weight[0].numel() % args.group_size)}
+               if args.granularity == "group" else {})}, clip_search=searched,
             **({"mx_scales": {k: v["scales"] for k, v in state.items()}} if args.mx_scale_search else {}))
         with open(args.report, "w") as f:
             json.dump(rep, f, indent=1, allow_nan=False)

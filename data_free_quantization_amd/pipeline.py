@@ -36,7 +36,7 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
             symmetric: bool = False, bc_mode: str = "literal", clip_range=(-15, 15),
             stage_hook: Optional[Callable[[str], None]] = None, timings: Optional[Dict] = None,
             report: Optional[dict] = None, clip_search: Optional[dict] = None, weight_format: str = "int",
-            mx_scale_search: bool = False):
+            mx_scale_search: bool = False, group_size: Optional[int] = None):
     """Run the DFQ stages on ``model`` (already on the GPU) in place; returns the
     equalization relations.  ``report``: a dict to fill with the quality report
     (quality.weight_report) of the quantized weights against their values after
@@ -59,11 +59,21 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
     the better of the floor rule's scale and the next one up by its own quantization noise
     (quantize_targ_layer(mx_scale_search=True)).  The report's config then
     holds ``mx_scale_search`` and each layer ``scale_raised``, the blocks that took the higher
-    scale.  Off: no new key, no new launch."""
+    scale.  Off: no new key, no new launch.
+    ``granularity="group"`` with ``group_size=g``: group-wise integer weights
+    (quantize_targ_layer(granularity="group"): layers whose row length is a multiple of g in
+    groups of g, the others per channel); the report's config holds ``group_size``.  ValueError
+    with an MX ``weight_format``, ``clip_search`` and ``bc_mode="fused"`` under ``correction``
+    (the group-wise sweep writes no error sums)."""
     from .mx import bits_per_weight, is_mx
     mx_fmt = is_mx(weight_format)
     if mx_scale_search and not mx_fmt:
         raise ValueError("mx_scale_search needs an MX weight_format, got %r" % (weight_format,))
+    if (granularity == "group") != (group_size is not None):
+        raise ValueError("granularity='group' and group_size go together")
+    if granularity == "group" and (mx_fmt or clip_search is not None or (correction and bc_mode == "fused")):
+        raise ValueError("granularity='group' does not apply to an MX weight_format, clip_search or the fused "
+                         "bias-correction hand-off (the group-wise sweep writes no error sums)")
     if mx_fmt:
         if clip_search is not None:
             raise ValueError("weight_format=%r conflicts with clip_search: the search minimizes an integer "
@@ -126,7 +136,8 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
         stage("quant", quantize_targ_layer, graph, bits_weight, bits_bias, targ, granularity=granularity,
               symmetric=symmetric, clip=fused_clip, state=qstate, weight_ranges=fold_ranges,
               **({"weight_format": weight_format} if mx_fmt else {}),
-              **({"mx_scale_search": True} if mx_scale_search else {}))
+              **({"mx_scale_search": True} if mx_scale_search else {}),
+              **({"group_size": group_size} if granularity == "group" else {}))
     if clip and not (quantize and bc_mode == "fused"):
         stage("clip", clip_weight, graph, range_clip=list(clip_range), targ_type=targ)
     if snap is not None:   # the weights are final from here (bias correction rewrites biases only)
@@ -135,7 +146,8 @@ def run_dfq(model: nn.Module, graph, bottoms, targ, *, relu: bool = True, equali
             "equalize": bool(equalize), "absorption": bool(absorption), "clip": bool(clip),
             "clip_range": [float(c) for c in clip_range], "bc_mode": bc_mode, **cs_cfg,
             **({"weight_format": weight_format, "bits_per_weight": bits_per_weight(weight_format)} if mx_fmt else {}),
-            **({"mx_scale_search": True} if mx_scale_search else {})},
+            **({"mx_scale_search": True} if mx_scale_search else {}),
+            **({"group_size": group_size} if granularity == "group" else {})},
             clip_search=searched,
             **({"mx_scales": {k: v["scales"] for k, v in qstate.items()}} if mx_scale_search else {})))
     if correction:

@@ -207,7 +207,7 @@ def _identity_forward(bn):
 def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, *, granularity="tensor",
                         symmetric=False, clip=None, state: Optional[Dict] = None, shard: bool = False,
                         group=None, weight_ranges: Optional[Dict] = None, weight_format: str = "int",
-                        mx_scale_search: bool = False, rounding: str = "nearest"):
+                        mx_scale_search: bool = False, rounding: str = "nearest", group_size: Optional[int] = None):
     """Fake-quantize every target layer's weight (and bias when bits_bias < 32) in
     place, all layers in one grouped launch.
 
@@ -253,8 +253,28 @@ def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, *, gr
     and ``flips`` (int32 [rows, 2]: kernel-stage and channel-stage flips per row).  The
     call writes no error sums, so the fused bias-correction hand-off is out of scope:
     asking such an entry for ``esum`` raises ValueError, as do an MX ``weight_format``,
-    ``clip=`` (clamp first with ``clip_weight`` / ``search_clip``) and ``shard=True``."""
+    ``clip=`` (clamp first with ``clip_weight`` / ``search_clip``) and ``shard=True``.
+
+    ``granularity="group"`` with ``group_size=g`` (not ``group=``, the process group): an
+    fp32 scale and zero per g consecutive elements of a weight row, the operand of
+    ``intmm.int_gemm(b_group=g)``.  Nearest rounding on the integer sweep only.  The rule: a
+    layer whose row length K (= in_channels / groups * KH * KW) is a multiple of g is swept
+    per channel as [N * K / g, g] rows; any other layer (a 3 x 3 stem's 27, a depthwise 9)
+    falls back to per channel.  ``state[k]`` holds ``codes``, ``scale`` and ``zero`` --
+    [N, K / g], or [N] after the fallback -- ``khw`` and ``group_size`` (g, or None after the
+    fallback).  The sweep's error sums need rows that are whole kernels (row_len % khw == 0),
+    which a group of a k x k layer is not, so the call writes none: asking an entry for
+    ``esum`` raises ValueError, as do ``rounding="sum"``, ``shard=True`` and an MX
+    ``weight_format``."""
     from ..mx import is_mx
+    if granularity == "group":
+        if rounding != "nearest" or shard or is_mx(weight_format) or mx_scale_search:
+            raise ValueError("granularity='group' is the integer sweep with nearest rounding, unsharded: it does not "
+                             "apply to rounding=%r, shard=%r, weight_format=%r" % (rounding, shard, weight_format))
+        return _quantize_targ_layer_group(graph, bit_weight, bits_bias, targ_type, group_size=group_size,
+                                          symmetric=symmetric, clip=clip, state=state)
+    if group_size is not None:
+        raise ValueError("group_size needs granularity='group'")
     if rounding not in ("nearest", "sum"):
         raise ValueError("rounding must be 'nearest' or 'sum', got %r" % (rounding,))
     if rounding == "sum":
@@ -331,6 +351,57 @@ def quantize_targ_layer(graph, bit_weight=8, bits_bias=16, targ_type=None, *, gr
         wk = [k for k in keys if k is not None]
         for k, it, sp in zip(wk, wl, spans):
             state[k] = _StateEntry(codes, f32, sp, tuple(it.src.shape), it.khw, up)
+    return graph
+
+
+class _GroupState(dict):
+    """A layer's state entry under granularity="group": no error sums are written."""
+
+    def __missing__(self, key):
+        if key == "esum":
+            raise ValueError("granularity='group' writes no error sums (esum): a group is no whole number of kernels")
+        raise KeyError(key)
+
+
+def _quantize_targ_layer_group(graph, bit_weight, bits_bias, targ_type, *, group_size, symmetric, clip, state):
+    """quantize_targ_layer with granularity="group" (see there): one sweep for all layers."""
+    assert targ_type is not None, "targ_type cannot be None!"
+    if group_size is None or int(group_size) < 1:
+        raise ValueError("granularity='group' needs group_size >= 1, got %r" % (group_size,))
+    g = int(group_size)
+    _lib.weights_changed()
+    print("Quantizing Layer parameters (groups of %d)" % g)
+    items, entries = [], {}
+    tt = tuple(targ_type)
+    cdt = (torch.int8 if symmetric else torch.uint8) if bit_weight <= 8 else torch.int16
+    for layer_idx, layer in graph.items():
+        if type(layer) not in tt:
+            continue
+        layer.__dict__.pop("weight_format", None)   # an earlier MX pass's marks
+        layer.__dict__.pop("mx_scale_search", None)
+        lp = layer._parameters
+        w = lp["weight"]
+        N, K = w.size(0), w[0].numel()
+        grouped = K % g == 0
+        rows = N * (K // g) if grouped else N
+        it = SweepItem(src=w, dst=w, bits=bit_weight, per_channel=True, symmetric=symmetric, clip=clip, rows=rows)
+        if state is not None:
+            it.codes = torch.empty(w.shape, dtype=cdt, device=w.device)
+            it.scale, it.zero = (torch.empty((N, K // g) if grouped else (N,), dtype=torch.float32, device=w.device)
+                                 for _ in range(2))
+            entries[layer_idx] = _GroupState(codes=it.codes, scale=it.scale, zero=it.zero, khw=khw_of(w),
+                                             group_size=g if grouped else None)
+        items.append(it)
+        if lp.get("bias") is not None and bits_bias < 32:
+            b = lp["bias"]
+            items.append(SweepItem(src=b, dst=b, bits=bits_bias, per_channel=False, symmetric=False, rows=1))
+    if not items:
+        return graph
+    plan = SweepPlan(items)
+    plan.execute()
+    plan.destroy()
+    if state is not None:
+        state.update(entries)
     return graph
 
 

@@ -887,6 +887,43 @@ typedef struct dfq_int_conv2d_desc {
 } dfq_int_conv2d_desc;
 int dfq_int_conv2d(const dfq_int_conv2d_desc* d, void* stream);
 
+/* ---- group-wise B parameters for the three entries above (no reference counterpart) ----
+ * dfq_int_gemm, dfq_int_linear and dfq_int_conv2d with an fp32 scale and zero per b_group
+ * consecutive elements of a row of B -- the layout of deployed W4 formats -- in place of one per
+ * tensor or per row.  The descriptors are the old entries'; DFQ_INT_B_PER_ROW must be clear, and
+ * b_scale / b_zero (optional) hold N * G fp32 values, row-major [N][G], 4-B aligned, with
+ *   g = b_group,   G = ceil(K / g),   group j covers k in [j g, min((j + 1) g, K)),
+ * so the last group of a row may be short.  With the exact integers per group
+ *   P_j[m][n] = sum_{k in j} qa qb     Sa_j[m] = sum_{k in j} qa
+ *   Sb_j[n]   = sum_{k in j} qb        K_j     = |group j|
+ * the result is
+ *   for j = 0 .. G - 1:
+ *     acc (= for the very first term, += after)  ((double)sa * (double)sb[n][j]) * (double)P_j
+ *     acc += ((double)sa * (double)zb[n][j]) * (double)Sa_j[m]      -- if b_zero
+ *     acc += ((double)za * (double)sb[n][j]) * (double)Sb_j[n]      -- if a_zero
+ *     acc += ((double)za * (double)zb[n][j]) * (double)K_j          -- if both
+ *   acc += (double)bias[n]                                          -- if bias
+ *   out  = (float)acc
+ * in fp64, one IEEE operation per line, no contraction, groups in ascending j.  The first term
+ * assigns -- it is not added to 0.0 -- so a call with g >= K (one group) gives the bits of the old
+ * entry's DFQ_INT_B_PER_ROW call, a -0.0 included.  For the convolution the sums carry the tap
+ * mask v as dfq_int_conv2d's do (P_j = sum_{k in j} v qa qb, ...), K_j becomes
+ * T_j[m] = sum_{k in j} v per row and per group, the groups run along (c, kh, kw), the order the
+ * weight is stored in, za is always present and the term order inside a group is
+ * dfq_int_conv2d's.
+ * b_group is 32, or a multiple of 64 up to DFQ_INT_MAX_K.  The integer accumulators of the old
+ * kernel hold one group's sums; each output has one double running sum in its lane that takes
+ * the group's steps when the group closes.  A multiple of 64 closes between two K steps; 32 is
+ * half a step, which then runs as two passes, each with the A-side operands zero in the lanes
+ * that hold the other half (sixteen instructions a step instead of eight).  Under a tap mask
+ * T_j comes from one more instruction per row tile (mask x all-ones).  No LDS, no atomics, no
+ * split of K, no workspace: the same bits from run to run and across the load paths.
+ * Checks: the old entry's, then DFQ_ERR_INVALID for b_group < 1 or DFQ_INT_B_PER_ROW set, and
+ * DFQ_ERR_UNSUPPORTED for any other b_group. */
+int dfq_int_gemm_grouped(const dfq_int_gemm_desc* d, int32_t b_group, void* stream);
+int dfq_int_linear_grouped(const dfq_int_linear_desc* d, int32_t b_group, void* stream);
+int dfq_int_conv2d_grouped(const dfq_int_conv2d_desc* d, int32_t b_group, void* stream);
+
 /* ---- integer depthwise convolution in one launch (packed 8-bit dot products) ----
  * dfq_int_conv2d's statement for groups == C: output channel n of N = C * mult reads input
  * channel c = n / mult and nothing else, so K = KH * KW.  With
