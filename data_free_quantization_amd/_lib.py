@@ -43,6 +43,7 @@ EXPORTS = [
     "dfq_mx_linear", "dfq_mx_conv2d",
     "dfq_int_gemm", "dfq_int_linear", "dfq_int_conv2d", "dfq_int_dwconv2d",
     "dfq_int_gemm_grouped", "dfq_int_linear_grouped", "dfq_int_conv2d_grouped",
+    "dfq_int_gemm_q", "dfq_int_linear_q", "dfq_int_conv2d_q", "dfq_int_dwconv2d_q",
 ]
 #: entry points only the diagnostics library exports (include/dfq_diag.h)
 DIAG_EXPORTS = ["dfq_probe_stream", "dfq_probe_lds", "dfq_debug_timeline", "dfq_debug_ablate",
@@ -194,6 +195,13 @@ class IntDwConv2dDesc(C.Structure):
     _fields_ = [(("mult", t) if f == "N" else (f, t)) for f, t in IntConv2dDesc._fields_]   # N = C * mult
 
 
+class IntIo(C.Structure):
+    _fields_ = [
+        ("x_codes", C.c_int32), ("out_bits", C.c_int32), ("out_symmetric", C.c_int32), ("out_flags", C.c_int32),
+        ("out_min_dev", C.c_void_p), ("out_max_dev", C.c_void_p), ("out_given_min", C.c_double), ("out_given_max", C.c_double),
+    ]
+
+
 DFQ_BC_OP_EXPECT, DFQ_BC_OP_APPLY, DFQ_BC_OP_PROPAGATE, DFQ_BC_OP_COPY = 0, 1, 2, 3
 DFQ_BC_APPLY_VEC_SCRATCH = 1
 DFQ_BN_FOLD_ZERO_BIAS = 1
@@ -301,6 +309,10 @@ def load(path: Optional[os.PathLike] = None) -> C.CDLL:
         "dfq_int_gemm_grouped": ([C.POINTER(IntGemmDesc), C.c_int32, P], C.c_int),
         "dfq_int_linear_grouped": ([C.POINTER(IntLinearDesc), C.c_int32, P], C.c_int),
         "dfq_int_conv2d_grouped": ([C.POINTER(IntConv2dDesc), C.c_int32, P], C.c_int),
+        "dfq_int_gemm_q": ([C.POINTER(IntGemmDesc), C.POINTER(IntIo), P], C.c_int),
+        "dfq_int_linear_q": ([C.POINTER(IntLinearDesc), C.POINTER(IntIo), P], C.c_int),
+        "dfq_int_conv2d_q": ([C.POINTER(IntConv2dDesc), C.POINTER(IntIo), P], C.c_int),
+        "dfq_int_dwconv2d_q": ([C.POINTER(IntDwConv2dDesc), C.POINTER(IntIo), P], C.c_int),
     }
     diag = {
         "dfq_probe_stream": ([P, P, P, P, I64, I32, P], C.c_int),

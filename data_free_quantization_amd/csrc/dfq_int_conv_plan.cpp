@@ -4,7 +4,7 @@
 
 namespace dfq {
 
-int igc_check(const dfq_int_conv2d_desc* d, MxcGeom& g, int64_t& M, int64_t& K, int64_t& grid) {
+int igc_check(const dfq_int_conv2d_desc* d, MxcGeom& g, int64_t& M, int64_t& K, int64_t& grid, unsigned bytes) {
     const auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
     g = MxcGeom{};
     M = K = grid = 0;
@@ -18,7 +18,7 @@ int igc_check(const dfq_int_conv2d_desc* d, MxcGeom& g, int64_t& M, int64_t& K, 
     if (d->x_bits < 2 || d->x_bits > 8) return DFQ_ERR_INVALID;
     int rc = mxc_check_extents(*d);
     if (rc != DFQ_OK) return rc;
-    if (addr(d->x) % 4 || addr(d->out) % 4 || addr(d->bias) % 4 || addr(d->min_dev) % 4 || addr(d->max_dev) % 4) return DFQ_ERR_INVALID;
+    if ((!(bytes & kIgBytesX) && addr(d->x) % 4) || (!(bytes & kIgBytesOut) && addr(d->out) % 4) || addr(d->bias) % 4 || addr(d->min_dev) % 4 || addr(d->max_dev) % 4) return DFQ_ERR_INVALID;
     if (addr(d->b_codes) % 16 || addr(d->b_scale) % 4 || addr(d->b_zero) % 4) return DFQ_ERR_INVALID;
     int64_t n = 0;
     rc = mxc_check_geometry(*d, g, M, K, n);

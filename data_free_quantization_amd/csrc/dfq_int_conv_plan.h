@@ -63,6 +63,6 @@ DFQ_HOST_DEVICE inline int64_t igc_fold_s(int64_t r, int o, int64_t T) { return 
 
 // dfq_int_conv2d's argument checks (no device call): DFQ_OK with the geometry, M, K and the
 // grid, or the error.
-int igc_check(const dfq_int_conv2d_desc* d, MxcGeom& g, int64_t& M, int64_t& K, int64_t& grid);
+int igc_check(const dfq_int_conv2d_desc* d, MxcGeom& g, int64_t& M, int64_t& K, int64_t& grid, unsigned bytes = 0);   // bytes: kIgBytesX | kIgBytesOut
 
 }  // namespace dfq

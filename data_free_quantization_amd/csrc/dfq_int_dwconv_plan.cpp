@@ -4,7 +4,7 @@
 
 namespace dfq {
 
-int dwc_check(const dfq_int_dwconv2d_desc* d, DwcGeom& g, int64_t& grid) {
+int dwc_check(const dfq_int_dwconv2d_desc* d, DwcGeom& g, int64_t& grid, unsigned bytes) {
     const auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
     g = DwcGeom{};
     grid = 0;
@@ -25,7 +25,7 @@ int dwc_check(const dfq_int_dwconv2d_desc* d, DwcGeom& g, int64_t& grid) {
     const int64_t N = d->C * d->mult;
     if (N > kMax) return DFQ_ERR_INVALID;
     if (d->H * d->W >= k31 || d->C * (d->H * d->W) >= k31) return DFQ_ERR_INVALID;
-    if (addr(d->x) % 4 || addr(d->out) % 4 || addr(d->bias) % 4 || addr(d->min_dev) % 4 || addr(d->max_dev) % 4) return DFQ_ERR_INVALID;
+    if ((!(bytes & kIgBytesX) && addr(d->x) % 4) || (!(bytes & kIgBytesOut) && addr(d->out) % 4) || addr(d->bias) % 4 || addr(d->min_dev) % 4 || addr(d->max_dev) % 4) return DFQ_ERR_INVALID;
     if (addr(d->b_codes) % 16 || addr(d->b_scale) % 4 || addr(d->b_zero) % 4) return DFQ_ERR_INVALID;
     const int64_t OH = mxc_out_extent(d->H, d->pad_h, d->dil_h, d->KH, d->stride_h);
     const int64_t OW = mxc_out_extent(d->W, d->pad_w, d->dil_w, d->KW, d->stride_w);

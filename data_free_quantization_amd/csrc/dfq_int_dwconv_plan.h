@@ -191,6 +191,6 @@ DFQ_HOST_DEVICE inline int64_t dwc_out_offset(const DwcGeom& g, int64_t p, int32
 
 // dfq_int_dwconv2d's argument checks (no device call): DFQ_OK with the geometry and the grid, or
 // the error.
-int dwc_check(const dfq_int_dwconv2d_desc* d, DwcGeom& g, int64_t& grid);
+int dwc_check(const dfq_int_dwconv2d_desc* d, DwcGeom& g, int64_t& grid, unsigned bytes = 0);   // bytes: kIgBytesX | kIgBytesOut
 
 }  // namespace dfq

@@ -83,8 +83,10 @@ DFQ_HOST_DEVICE inline int64_t ig_fold_s(int64_t r, int o, int64_t K) { return r
 // The argument checks both entry points share (no device call): DFQ_OK and the grid, or the
 // error.  a_ok: A's own pointers are there, aligned, and its fields in range; lda: x's row
 // stride (K for stored codes, so that its check passes whenever K's do).
+// bytes (the code-in / code-out entries, dfq_int_io_plan.h): x / out hold code bytes, 1-B aligned.
+constexpr unsigned kIgBytesX = 1, kIgBytesOut = 2;
 template <class Desc>
-inline int ig_check_common(const Desc& d, bool a_ok, int64_t lda, int32_t known_flags, int64_t& grid) {
+inline int ig_check_common(const Desc& d, bool a_ok, int64_t lda, int32_t known_flags, int64_t& grid, unsigned bytes = 0) {
     const auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
     if (!a_ok || !d.b_codes || !d.b_scale || !d.out) return DFQ_ERR_INVALID;
     if ((d.flags & ~known_flags) != 0 || d.reserved != 0) return DFQ_ERR_INVALID;
@@ -93,7 +95,7 @@ inline int ig_check_common(const Desc& d, bool a_ok, int64_t lda, int32_t known_
     if (d.M > (int64_t(1) << 40) || d.N > (int64_t(1) << 40) || d.ldo > (int64_t(1) << 40) || lda > (int64_t(1) << 40))
         return DFQ_ERR_INVALID;
     if (addr(d.b_codes) % 16) return DFQ_ERR_INVALID;
-    if (addr(d.out) % 4 || addr(d.bias) % 4 || addr(d.b_scale) % 4 || addr(d.b_zero) % 4) return DFQ_ERR_INVALID;
+    if ((!(bytes & kIgBytesOut) && addr(d.out) % 4) || addr(d.bias) % 4 || addr(d.b_scale) % 4 || addr(d.b_zero) % 4) return DFQ_ERR_INVALID;
     if (lda < d.K || d.ldo < d.N) return DFQ_ERR_SHAPE;
     if (d.M > (int64_t(1) << 50) / lda || d.M > (int64_t(1) << 50) / d.ldo) return DFQ_ERR_INVALID;   // row * ld + col
     if (d.K > kIgMaxK) return DFQ_ERR_UNSUPPORTED;
@@ -104,8 +106,8 @@ inline int ig_check_common(const Desc& d, bool a_ok, int64_t lda, int32_t known_
     return DFQ_OK;
 }
 
-int ig_check(const dfq_int_gemm_desc* d, int64_t& grid);
-int igl_check(const dfq_int_linear_desc* d, int64_t& grid);
+int ig_check(const dfq_int_gemm_desc* d, int64_t& grid, unsigned bytes = 0);
+int igl_check(const dfq_int_linear_desc* d, int64_t& grid, unsigned bytes = 0);
 
 // ---- group-wise B parameters (dfq_int_*_grouped; dfq_int_group.hip) ----
 // b_scale / b_zero hold [N][G] values, G = ceil(K / g); group j covers k in [j g, min((j + 1) g, K)).

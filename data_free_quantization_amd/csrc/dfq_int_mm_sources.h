@@ -1,13 +1,15 @@
 // The fragment sources and stores of the integer matrix multiply kernels (dfq_int_gemm.hip:
 // int_mm_kernel; dfq_int_group.hip: int_mm_group_kernel): how a lane obtains the 16 bytes of its A
 // fragment (stored codes, fp32 x quantized on the way, im2col rows gathered and quantized on the
-// way), of its B fragment (stored bytes, packed nibbles), and where a result goes (row-major,
-// NCHW).  Device code: included by the two kernel files and nothing else.
+// way, im2col rows gathered from stored codes), of its B fragment (stored bytes, packed nibbles),
+// and where a result goes (row-major or NCHW, as fp32 or as the next layer's code bytes).  Device
+// code: included by the kernel files (dfq_int_mm_kernel.h, dfq_int_group.hip) and nothing else.
 #pragma once
 #include "dfq_common.h"
 
 #include "dfq_int_conv_plan.h"
 #include "dfq_int_gemm_plan.h"
+#include "dfq_int_io_plan.h"
 #include "dfq_int_quant.h"
 
 namespace dfq {
@@ -249,11 +251,56 @@ struct IgConvA {
     }
 };
 
+// A = the stored codes of an NCHW activation (dfq_int_conv2d_q with x_codes): IgConvA's rows, tap
+// walker and mask, the lane's run of 16 consecutive k gathered as byte loads straight into the
+// fragment's four words.  No quantizer and no ballot: the range of the descriptor only names the
+// grid (params(): sa, za, the xor mask).  A padding tap, a column >= K and a row >= M are loads
+// not issued and clear mask bits, 0 in the signed domain.  Where IgConvA holds 16 floats between
+// the loads and the top of the step, this holds 16 bytes.
+template <bool PW, bool MASK>
+struct IgConvCodesA : IgConvA<PW, MASK> {
+    typedef IgcArgs Args;
+    typedef MxcRow Row;
+    struct Fetched {
+        uint32_t w[4];
+        uint32_t mask;
+    };
+    static __device__ __forceinline__ void fetch(Fetched& f, const Args& g, const Row& row, int64_t step, int lane) {
+        const DFQ_GLOBAL uint8_t* x = (const DFQ_GLOBAL uint8_t*)g.a;
+        const int64_t k0 = ig_lane_k0(step, lane);
+        MxcTap t = mxc_tap<PW>(g.c, k0);
+        uint32_t mask = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) f.w[j] = 0;
+#pragma unroll
+        for (int e = 0; e < kIgLaneK; ++e) {
+            const uint32_t bit = igc_mask_bit<PW>(g.c, row, t, k0 + e, g.K, e);
+            const uint32_t code = bit ? x[mxc_x_offset(row, t)] : 0u;
+            f.w[e >> 2] |= code << (8 * (e & 3));
+            mask |= bit;
+            mxc_next<PW>(g.c, t);
+        }
+        f.mask = mask;
+    }
+    static __device__ __forceinline__ ig_v4i operand(const Fetched& f, const IgAParams& p, int) {
+        ig_v4i v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = (int)igc_operand_word(f.w[j], p.xm, f.mask, j);
+        return v;
+    }
+    static __device__ __forceinline__ ig_v4i mask(const Fetched& f) {
+        ig_v4i v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = (int)igc_ones_word(f.mask, j);
+        return v;
+    }
+};
+
 // Where the result goes.  kGroups: the epilogue hands over a lane's four rows of a column at once
 // (rows that are not stored hold 0), else every stored element as it is made.  Row-major [M][ldo]:
 // dfq_int_gemm's and dfq_int_linear's.
 struct IgRowMajorStore {
-    static constexpr bool kGroups = false;
+    static constexpr bool kGroups = false, kCodes = false;
     static __device__ __forceinline__ void store(float v, const IgArgs& g, int64_t row, int64_t col) {
         ((DFQ_GLOBAL float*)g.out)[mxg_out_offset(row, col, g.ldo)] = v;
     }
@@ -263,7 +310,7 @@ struct IgRowMajorStore {
 // element by element.
 typedef float ig_v4f_a4 __attribute__((ext_vector_type(4), aligned(4)));
 struct IgNchwStore {
-    static constexpr bool kGroups = true;
+    static constexpr bool kGroups = true, kCodes = false;
     static __device__ __forceinline__ void store(const float (&v)[4], const IgcArgs& g, int64_t m, int64_t col) {
         DFQ_GLOBAL float* out = (DFQ_GLOBAL float*)g.out;
         if (mxc_out_quad(g.c, m, g.M)) {
@@ -273,6 +320,48 @@ struct IgNchwStore {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 if (mxg_stores(m + r, col, g.M, g.N)) out[mxc_out_offset(g.c, m + r, col)] = v[r];
+        }
+    }
+};
+
+// The code stores (dfq_int_*_q with out_bits): the epilogue quantizes a lane's four rows of a
+// column with one ig_codes4 call -- every lane of a working wave, rows and columns that are not
+// stored carrying 0 -- and hands over the word of four code bytes; only the store is guarded.
+// IgOutQ: the output quantizer's arguments, dfq_fake_quant_given's.
+struct IgOutQ {
+    const float* min_dev;
+    const float* max_dev;
+    double gmin, gmax;
+    int bits, symmetric, flags;
+};
+inline IgOutQ ig_out_q(const dfq_int_io* io) {
+    return IgOutQ{io->out_min_dev, io->out_max_dev, io->out_given_min, io->out_given_max, io->out_bits, io->out_symmetric, io->out_flags};
+}
+__device__ __forceinline__ IgAParams ig_out_params(const IgOutQ& o) {
+    return ig_quant_params(o.min_dev, o.max_dev, o.gmin, o.gmax, o.bits, o.symmetric, o.flags);
+}
+// Row-major bytes [M][ldo]: byte stores.
+struct IgRowMajorCodeStore {
+    static constexpr bool kGroups = true, kCodes = true;
+    static __device__ __forceinline__ void store(uint32_t w, const IgArgs& g, int64_t m, int64_t col) {
+        DFQ_GLOBAL uint8_t* out = (DFQ_GLOBAL uint8_t*)g.out;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (mxg_stores(m + r, col, g.M, g.N)) out[mxg_out_offset(m + r, col, g.ldo)] = (uint8_t)(w >> (8 * r));
+    }
+};
+// NCHW bytes: one 4-B store where the four rows lie in one image and the address allows
+// (igio_out_word), else byte stores.
+struct IgNchwCodeStore {
+    static constexpr bool kGroups = true, kCodes = true;
+    static __device__ __forceinline__ void store(uint32_t w, const IgcArgs& g, int64_t m, int64_t col) {
+        DFQ_GLOBAL uint8_t* out = (DFQ_GLOBAL uint8_t*)g.out;
+        if (col < g.N && igio_out_word(g.c, m, g.M, col, reinterpret_cast<uintptr_t>(g.out))) {
+            *(DFQ_GLOBAL uint32_t*)(out + mxc_out_offset(g.c, m, col)) = w;
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (mxg_stores(m + r, col, g.M, g.N)) out[mxc_out_offset(g.c, m + r, col)] = (uint8_t)(w >> (8 * r));
         }
     }
 };

@@ -11,11 +11,15 @@ the real value 0; ``int_dwconv2d`` is the depthwise convolution (groups == C) on
 and the affine terms are applied in fp64 in a fixed order, so every output is bit for bit a
 numpy float64 statement (tests/int_gemm_cases.py).  ``b_group`` (``int_gemm``, ``int_linear``)
 and ``int_conv2d_grouped`` take group-wise weight parameters, a scale and zero per 32, 64, 128, ...
-elements of a weight row (``group_quant`` writes them; tests/int_group_cases.py).  There is no CPU
-fallback: CPU tensors raise."""
+elements of a weight row (``group_quant`` writes them; tests/int_group_cases.py).  ``out_quant``
+(``int_gemm``, ``int_linear``) and ``int_conv2d_q`` / ``int_dwconv2d_q`` store the next layer's
+activation codes instead of fp32, and the two convolutions read such codes (``x_codes``), so a
+run of layers exchanges uint8 tensors (tests/int_io_cases.py).  There is no CPU fallback: CPU
+tensors raise."""
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import Optional
 
 import torch
@@ -107,24 +111,95 @@ def _b_args(d, b_codes, b_scale, b_zero, K: int, b_packed: bool, b_group: Option
     return N
 
 
-def _range_args(d, min_dev, max_dev, min_value, max_value, scale_f32: bool) -> None:
-    """The quantizer's range: its checks and descriptor fields (int_linear's and int_conv2d's)."""
+def _range_fields(min_dev, max_dev, min_value, max_value, scale_f32: bool):
+    """A quantizer's range: its checks; (min_dev, max_dev, given_min, given_max, flags) as a descriptor or io struct takes them."""
     for name, dev_v, host_v in (("min", min_dev, min_value), ("max", max_dev, max_value)):
         if dev_v is not None:
             _param_arg(name + "_dev", dev_v, (1,))
         elif host_v is None:
             raise ValueError("the range's %s is missing: pass %s_dev or %s_value" % (name, name, name))
-    d.min_dev = min_dev.data_ptr() if min_dev is not None else None
-    d.max_dev = max_dev.data_ptr() if max_dev is not None else None
-    d.given_min = float(min_value) if min_value is not None else 0.0
-    d.given_max = float(max_value) if max_value is not None else 0.0
-    d.flags = _lib.DFQ_SCALE_F32 if scale_f32 else 0
+    return (min_dev.data_ptr() if min_dev is not None else None, max_dev.data_ptr() if max_dev is not None else None,
+            float(min_value) if min_value is not None else 0.0, float(max_value) if max_value is not None else 0.0,
+            _lib.DFQ_SCALE_F32 if scale_f32 else 0)
 
 
-def _launch(name: str, d, b_group: Optional[int], dev) -> None:
-    """The entry point ``name``, or its ``_grouped`` form under a group size."""
+def _range_args(d, min_dev, max_dev, min_value, max_value, scale_f32: bool) -> None:
+    """The input quantizer's range (int_linear's and the convolutions')."""
+    d.min_dev, d.max_dev, d.given_min, d.given_max, d.flags = _range_fields(min_dev, max_dev, min_value, max_value, scale_f32)
+
+
+@dataclass
+class OutQuant:
+    """The grid a call stores its result on as codes (dfq_int_io): ``fake_quant_given``'s
+    arguments -- ``bits`` 2..8, ``symmetric`` (int8 bytes, else uint8), the range from the device
+    scalars ``min_dev`` / ``max_dev`` or the Python floats ``min_value`` / ``max_value``,
+    ``scale_f32`` as there.  On a range with min = 0 (and max <= 6) the clamp is the ReLU (ReLU6)."""
+    bits: int = 8
+    symmetric: bool = False
+    min_dev: Optional[torch.Tensor] = None
+    max_dev: Optional[torch.Tensor] = None
+    min_value: Optional[float] = None
+    max_value: Optional[float] = None
+    scale_f32: bool = False
+
+
+def _code_dtype(symmetric) -> torch.dtype:
+    return torch.int8 if symmetric else torch.uint8
+
+
+def _io_arg(out_quant: Optional[OutQuant], x_codes: bool) -> Optional[_lib.IntIo]:
+    """The io struct of a call, None when the call is the old entry's; ``out_quant``'s checks."""
+    if out_quant is None and not x_codes:
+        return None
+    io = _lib.IntIo()
+    io.x_codes = int(bool(x_codes))
+    if out_quant is None:
+        return io
+    if not isinstance(out_quant, OutQuant):
+        raise TypeError("out_quant: an intmm.OutQuant")
+    if not 2 <= int(out_quant.bits) <= 8:
+        raise ValueError("out_quant.bits must be 2..8, got %d" % out_quant.bits)
+    io.out_min_dev, io.out_max_dev, io.out_given_min, io.out_given_max, io.out_flags = _range_fields(
+        out_quant.min_dev, out_quant.max_dev, out_quant.min_value, out_quant.max_value, out_quant.scale_f32)
+    if out_quant.min_dev is None and out_quant.max_dev is None and not io.out_given_max > io.out_given_min:
+        raise ValueError("out_quant: max_value must be above min_value")
+    io.out_bits, io.out_symmetric = int(out_quant.bits), int(bool(out_quant.symmetric))
+    return io
+
+
+def _code_out(what: str, shape, out, out_quant: OutQuant, dev, rows_strided: bool = False) -> torch.Tensor:
+    """The byte tensor a call with ``out_quant`` stores into: ``out``'s checks, or a new one."""
+    dtype = _code_dtype(out_quant.symmetric)
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != dtype:
+        raise TypeError("%s: out must be %s on the GPU under this out_quant" % (what, dtype))
+    ok = out.stride(-1) == 1 and (out.shape[0] == 1 or out.stride(0) >= shape[1]) if rows_strided and out.dim() == 2 else out.is_contiguous()
+    if tuple(out.shape) != tuple(shape) or not ok:
+        raise ValueError("%s: out must be a %s tensor%s" % (what, list(shape), " with unit column stride" if rows_strided else ", contiguous"))
+    return out
+
+
+def _bias_dev_args(what: str, N: int, dev, bias, tensors) -> None:
+    """``bias``'s checks and every tensor on one device (the convolutions', and a code output's)."""
+    if bias is not None:
+        _lib.require_device(bias)
+        if bias.numel() != N:
+            raise ValueError("bias holds %d elements, %d needed" % (bias.numel(), N))
+    for t in (*tensors, bias):
+        if t is not None and t.device != dev:
+            raise ValueError("every tensor of an %s call must live on one device" % what)
+
+
+def _launch(name: str, d, b_group: Optional[int], dev, io=None) -> None:
+    """The entry point ``name``, its ``_grouped`` form under a group size, or its ``_q`` form with an io struct."""
     L = _lib.load()
-    if b_group is None:
+    if io is not None:
+        if b_group is not None:
+            raise ValueError("stored activation codes and group-wise B do not combine")
+        name += "_q"
+        rc = getattr(L, name)(C.byref(d), C.byref(io), _lib.raw_stream(dev))
+    elif b_group is None:
         rc = getattr(L, name)(C.byref(d), _lib.raw_stream(dev))
     else:
         name += "_grouped"
@@ -132,9 +207,14 @@ def _launch(name: str, d, b_group: Optional[int], dev) -> None:
     _lib.check(rc, name, ValueError)
 
 
-def _bias_out_args(what: str, d, M: int, N: int, K: int, dev, bias, out, others) -> torch.Tensor:
-    """mx.py's checks of ``bias``, ``out`` and the tensors' device; the descriptor fields both entries share."""
-    out = mx._bias_out_args(what, M, N, dev, bias, out, others)
+def _bias_out_args(what: str, d, M: int, N: int, K: int, dev, bias, out, others, out_quant=None) -> torch.Tensor:
+    """mx.py's checks of ``bias``, ``out`` and the tensors' device; the descriptor fields both entries share.
+    Under ``out_quant`` ``out`` is a byte tensor and its row stride counts bytes."""
+    if out_quant is None:
+        out = mx._bias_out_args(what, M, N, dev, bias, out, others)
+    else:
+        out = _code_out(what, (M, N), out, out_quant, dev, rows_strided=True)
+        _bias_dev_args(what, N, dev, bias, (*others, out_quant.min_dev, out_quant.max_dev, out))
     d.bias = bias.data_ptr() if bias is not None else None
     d.out, d.ldo = out.data_ptr(), (out.stride(0) if M > 1 else max(out.stride(0), N))
     d.M, d.N, d.K = M, N, K
@@ -144,7 +224,7 @@ def _bias_out_args(what: str, d, M: int, N: int, K: int, dev, bias, out, others)
 def int_gemm(a_codes: torch.Tensor, a_scale: torch.Tensor, a_zero: Optional[torch.Tensor], b_codes: torch.Tensor,
              b_scale: torch.Tensor, b_zero: Optional[torch.Tensor], K: int, *, b_packed: bool = False,
              bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-             b_group: Optional[int] = None) -> torch.Tensor:
+             b_group: Optional[int] = None, out_quant: Optional[OutQuant] = None) -> torch.Tensor:
     """out[m, n] = sum_k (qa[m, k] * sa + za) * (qb[n, k] * sb[n] + zb[n]) (+ bias[n]) on the
     i8 matrix instruction (dfq_int_gemm).  ``a_codes``: M * K bytes, ``b_codes``:
     N * K bytes -- or N * K / 2 packed bytes with ``b_packed`` (the sweep's ``pack_int4`` layout,
@@ -159,20 +239,26 @@ def int_gemm(a_codes: torch.Tensor, a_scale: torch.Tensor, a_zero: Optional[torc
     [N, ceil(K / b_group)] values, one per ``b_group`` consecutive elements of a row (the last
     group may be short; ``group_quant`` writes them), and the result is the grouped statement
     (dfq_int_gemm_grouped): the groups' fp64 terms in ascending order.  One group (b_group >= K)
-    gives the per-row call's bits.  A disallowed size or a wrong count raises ValueError."""
+    gives the per-row call's bits.  A disallowed size or a wrong count raises ValueError.
+
+    ``out_quant`` (an ``OutQuant``; dfq_int_gemm_q): the result is stored as codes -- byte [m, n]
+    is ``fake_quant``'s code of the fp32 statement above on ``out_quant``'s range, uint8, or int8
+    when symmetric -- and ``out``, if passed, is such a [M, N] byte tensor (rows may be strided).
+    Not with ``b_group``."""
     K = _k_arg(K)
     b_group = _group_arg(b_group)
+    io = _io_arg(out_quant, False)
     M = _codes_arg("a_codes", a_codes, K)
     _param_arg("a_scale", a_scale, (1,))
     _param_arg("a_zero", a_zero, (1,), optional=True)
     d = _lib.IntGemmDesc()
     N = _b_args(d, b_codes, b_scale, b_zero, K, bool(b_packed), b_group)
     dev = a_codes.device
-    out = _bias_out_args("int_gemm", d, M, N, K, dev, bias, out, (a_scale, a_zero, b_codes, b_scale, b_zero))
+    out = _bias_out_args("int_gemm", d, M, N, K, dev, bias, out, (a_scale, a_zero, b_codes, b_scale, b_zero), out_quant)
     d.a_codes, d.a_scale = a_codes.data_ptr(), a_scale.data_ptr()
     d.a_zero = a_zero.data_ptr() if a_zero is not None else None
     d.a_signed = int(a_codes.dtype == torch.int8)
-    _launch("dfq_int_gemm", d, b_group, dev)
+    _launch("dfq_int_gemm", d, b_group, dev, io)
     return out
 
 
@@ -189,18 +275,20 @@ def int_linear(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor, b_
                bits: int = 8, symmetric: bool = False, min_dev: Optional[torch.Tensor] = None,
                max_dev: Optional[torch.Tensor] = None, min_value=None, max_value=None, scale_f32: bool = False,
                b_packed: bool = False, bias: Optional[torch.Tensor] = None,
-               out: Optional[torch.Tensor] = None, b_group: Optional[int] = None) -> torch.Tensor:
+               out: Optional[torch.Tensor] = None, b_group: Optional[int] = None,
+               out_quant: Optional[OutQuant] = None) -> torch.Tensor:
     """``int_gemm`` with A given as fp32 ``x`` [M, K] and quantized to ``bits`` (2..8) inside the
     kernel (dfq_int_linear): the quantizer is ``fake_quant_given``'s -- the range from the
     device scalars ``min_dev`` / ``max_dev`` (no host synchronisation) or the Python floats
     ``min_value`` / ``max_value``, ``scale_f32`` as there -- and the codes of x never reach
     memory.  Bit for bit ``fake_quant`` of x on that range (codes, scale, zero) followed by
     ``int_gemm``.  ``x`` needs unit column stride; any row stride >= K is passed on (a column
-    slice of a wider tensor is read in place).  B, ``bias``, ``out`` and ``b_group`` as for
-    ``int_gemm``."""
+    slice of a wider tensor is read in place).  B, ``bias``, ``out``, ``b_group`` and ``out_quant``
+    (dfq_int_linear_q: the result stored as codes) as for ``int_gemm``."""
     global LINEAR_CALLS
     K = _k_arg(K)
     b_group = _group_arg(b_group)
+    io = _io_arg(out_quant, False)
     bits = int(bits)
     if not 2 <= bits <= 8:
         raise ValueError("bits must be 2..8, got %d" % bits)
@@ -214,10 +302,10 @@ def int_linear(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor, b_
     _range_args(d, min_dev, max_dev, min_value, max_value, scale_f32)
     N = _b_args(d, b_codes, b_scale, b_zero, K, bool(b_packed), b_group)
     M, dev = x.shape[0], x.device
-    out = _bias_out_args("int_linear", d, M, N, K, dev, bias, out, (min_dev, max_dev, b_codes, b_scale, b_zero))
+    out = _bias_out_args("int_linear", d, M, N, K, dev, bias, out, (min_dev, max_dev, b_codes, b_scale, b_zero), out_quant)
     d.x, d.ldx = x.data_ptr(), (x.stride(0) if M > 1 else max(x.stride(0), K))
     d.x_bits, d.x_symmetric = bits, int(bool(symmetric))
-    _launch("dfq_int_linear", d, b_group, dev)
+    _launch("dfq_int_linear", d, b_group, dev, io)
     LINEAR_CALLS += 1
     return out
 
@@ -257,16 +345,36 @@ def int_conv2d_grouped(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Te
                    min_dev, max_dev, min_value, max_value, scale_f32, b_packed, bias, out)
 
 
-def _conv2d(x, b_codes, b_scale, b_zero, kernel_size, stride, padding, dilation, b_group, bits, symmetric, min_dev, max_dev,
-            min_value, max_value, scale_f32, b_packed, bias, out) -> torch.Tensor:
-    """int_conv2d's and int_conv2d_grouped's checks and launch."""
-    global LINEAR_CALLS
+def _x_arg(x, bits, symmetric, x_codes: bool) -> int:
+    """The checks of a convolution's ``bits`` and of ``x``'s type: fp32, or under ``x_codes`` the bytes ``symmetric`` names."""
     bits = int(bits)
     if not 2 <= bits <= 8:
         raise ValueError("bits must be 2..8, got %d" % bits)
-    _on_gpu("x", x, "a float32 tensor")
-    if x.dtype != torch.float32:
+    if x_codes and isinstance(x, torch.Tensor) and x.dtype != _code_dtype(symmetric):
+        raise TypeError("x: stored codes are %s when symmetric=%s, got %s" % (_code_dtype(symmetric), bool(symmetric), x.dtype))
+    _on_gpu("x", x, "a uint8 or int8 tensor" if x_codes else "a float32 tensor")
+    if not x_codes and x.dtype != torch.float32:
         raise TypeError("x: float32 on the GPU")
+    return bits
+
+
+def _conv_out(what: str, shape, out, out_quant, dev) -> torch.Tensor:
+    if out_quant is not None:
+        return _code_out(what, shape, out, out_quant, dev)
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32:
+        raise TypeError("out: float32 on the GPU")
+    if tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous [%d, %d, %d, %d] tensor" % tuple(shape))
+    return out
+
+
+def _conv2d(x, b_codes, b_scale, b_zero, kernel_size, stride, padding, dilation, b_group, bits, symmetric, min_dev, max_dev,
+            min_value, max_value, scale_f32, b_packed, bias, out, io=None, out_quant=None) -> torch.Tensor:
+    """int_conv2d's, int_conv2d_grouped's and int_conv2d_q's checks and launch."""
+    global LINEAR_CALLS
+    bits = _x_arg(x, bits, symmetric, io is not None and io.x_codes)
     (KH, KW), (sh, sw) = mx._pair(kernel_size, "kernel_size"), mx._pair(stride, "stride")
     (ph, pw), (dh, dw) = mx._pair(padding, "padding"), mx._pair(dilation, "dilation")
     if min(KH, KW, sh, sw, dh, dw) < 1 or min(ph, pw) < 0:
@@ -282,26 +390,15 @@ def _conv2d(x, b_codes, b_scale, b_zero, kernel_size, stride, padding, dilation,
     if OH < 1 or OW < 1:
         raise ValueError("the kernel %s (dilation %s) does not fit the padded input %s" % ((KH, KW), (dh, dw), (H + 2 * ph, W + 2 * pw)))
     dev = x.device
-    if bias is not None:
-        _lib.require_device(bias)
-        if bias.numel() != N:
-            raise ValueError("bias holds %d elements, %d needed" % (bias.numel(), N))
-    if out is None:
-        out = torch.empty((B, N, OH, OW), dtype=torch.float32, device=dev)
-    else:
-        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32:
-            raise TypeError("out: float32 on the GPU")
-        if tuple(out.shape) != (B, N, OH, OW) or not out.is_contiguous():
-            raise ValueError("out must be a contiguous [%d, %d, %d, %d] tensor" % (B, N, OH, OW))
-    for t in (min_dev, max_dev, b_codes, b_scale, b_zero, bias, out):
-        if t is not None and t.device != dev:
-            raise ValueError("every tensor of an int_conv2d call must live on one device")
+    out = _conv_out("int_conv2d", (B, N, OH, OW), out, out_quant, dev)
+    _bias_dev_args("int_conv2d", N, dev, bias, (min_dev, max_dev, b_codes, b_scale, b_zero, out, getattr(out_quant, "min_dev", None),
+                                              getattr(out_quant, "max_dev", None)))
     d.x, d.out = x.data_ptr(), out.data_ptr()
     d.bias = bias.data_ptr() if bias is not None else None
     d.B, d.C, d.H, d.W, d.N, d.KH, d.KW = B, Cin, H, W, N, KH, KW
     d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w = sh, sw, ph, pw, dh, dw
     d.x_bits, d.x_symmetric = bits, int(bool(symmetric))
-    _launch("dfq_int_conv2d", d, b_group, dev)
+    _launch("dfq_int_conv2d", d, b_group, dev, io)
     LINEAR_CALLS += 1
     return out
 
@@ -323,13 +420,15 @@ def int_dwconv2d(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor, 
     ``kernel_size``, ``stride``, ``padding``, ``dilation``: ints or (h, w) pairs.  ``out``: fp32
     contiguous [B, N, OH, OW]; allocated when None.  Counts in ``LINEAR_CALLS``.  Asynchronous on
     the current stream; there is no CPU fallback."""
+    return _dwconv2d(x, b_codes, b_scale, b_zero, kernel_size, stride, padding, dilation, bits, symmetric, min_dev, max_dev,
+                     min_value, max_value, scale_f32, b_packed, bias, out)
+
+
+def _dwconv2d(x, b_codes, b_scale, b_zero, kernel_size, stride, padding, dilation, bits, symmetric, min_dev, max_dev,
+              min_value, max_value, scale_f32, b_packed, bias, out, io=None, out_quant=None) -> torch.Tensor:
+    """int_dwconv2d's and int_dwconv2d_q's checks and launch."""
     global LINEAR_CALLS
-    bits = int(bits)
-    if not 2 <= bits <= 8:
-        raise ValueError("bits must be 2..8, got %d" % bits)
-    _on_gpu("x", x, "a float32 tensor")
-    if x.dtype != torch.float32:
-        raise TypeError("x: float32 on the GPU")
+    bits = _x_arg(x, bits, symmetric, io is not None and io.x_codes)
     (KH, KW), (sh, sw) = mx._pair(kernel_size, "kernel_size"), mx._pair(stride, "stride")
     (ph, pw), (dh, dw) = mx._pair(padding, "padding"), mx._pair(dilation, "dilation")
     if min(KH, KW, sh, sw, dh, dw) < 1 or min(ph, pw) < 0:
@@ -349,28 +448,51 @@ def int_dwconv2d(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor, 
     if OH < 1 or OW < 1:
         raise ValueError("the kernel %s (dilation %s) does not fit the padded input %s" % ((KH, KW), (dh, dw), (H + 2 * ph, W + 2 * pw)))
     dev = x.device
-    if bias is not None:
-        _lib.require_device(bias)
-        if bias.numel() != N:
-            raise ValueError("bias holds %d elements, %d needed" % (bias.numel(), N))
-    if out is None:
-        out = torch.empty((B, N, OH, OW), dtype=torch.float32, device=dev)
-    else:
-        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32:
-            raise TypeError("out: float32 on the GPU")
-        if tuple(out.shape) != (B, N, OH, OW) or not out.is_contiguous():
-            raise ValueError("out must be a contiguous [%d, %d, %d, %d] tensor" % (B, N, OH, OW))
-    for t in (min_dev, max_dev, b_codes, b_scale, b_zero, bias, out):
-        if t is not None and t.device != dev:
-            raise ValueError("every tensor of an int_dwconv2d call must live on one device")
+    out = _conv_out("int_dwconv2d", (B, N, OH, OW), out, out_quant, dev)
+    _bias_dev_args("int_dwconv2d", N, dev, bias, (min_dev, max_dev, b_codes, b_scale, b_zero, out, getattr(out_quant, "min_dev", None),
+                                              getattr(out_quant, "max_dev", None)))
     d.x, d.out = x.data_ptr(), out.data_ptr()
     d.bias = bias.data_ptr() if bias is not None else None
     d.B, d.C, d.H, d.W, d.mult, d.KH, d.KW = B, Cin, H, W, N // Cin, KH, KW
     d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w = sh, sw, ph, pw, dh, dw
     d.x_bits, d.x_symmetric = bits, int(bool(symmetric))
-    _lib.check(_lib.load().dfq_int_dwconv2d(C.byref(d), _lib.raw_stream(dev)), "dfq_int_dwconv2d", ValueError)
+    _launch("dfq_int_dwconv2d", d, None, dev, io)
     LINEAR_CALLS += 1
     return out
+
+
+def int_conv2d_q(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor, b_zero: Optional[torch.Tensor], kernel_size,
+                 stride=1, padding=0, dilation=1, *, x_codes: bool = False, out_quant: Optional[OutQuant] = None, bits: int = 8,
+                 symmetric: bool = False, min_dev: Optional[torch.Tensor] = None, max_dev: Optional[torch.Tensor] = None,
+                 min_value=None, max_value=None, scale_f32: bool = False, b_packed: bool = False,
+                 bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``int_conv2d`` with stored activation codes at either end (dfq_int_conv2d_q).
+
+    ``x_codes``: ``x`` is a contiguous NCHW tensor of codes -- uint8, or int8 when ``symmetric``,
+    else TypeError -- and the range keywords and ``bits`` name the grid they are on: with (s, z)
+    ``fake_quant``'s scale and zero of that range, element q stands for q * s + z, exactly what the
+    in-kernel quantizer of ``int_conv2d`` would have derived from the fp32 values; nothing is
+    quantized on the way.  ``out_quant`` (an ``OutQuant``): byte [b, n, oh, ow] of the result is
+    ``fake_quant``'s code of ``int_conv2d``'s fp32 value there -- the same integers and fp64 steps,
+    bias included -- on ``out_quant``'s range, and ``out``, if passed, is a contiguous byte tensor.
+    So ``int_conv2d_q(x, ..., out_quant=r)`` followed by ``int_conv2d_q(codes, ..., x_codes=True,
+    **r's range)`` is bit for bit ``int_conv2d`` -> ``fake_quant_given`` -> ``int_conv2d`` with no
+    fp32 activation in memory.  With neither option the result is ``int_conv2d``'s."""
+    return _conv2d(x, b_codes, b_scale, b_zero, kernel_size, stride, padding, dilation, None, bits, symmetric, min_dev, max_dev,
+                   min_value, max_value, scale_f32, b_packed, bias, out, _io_arg(out_quant, x_codes) or _lib.IntIo(), out_quant)
+
+
+def int_dwconv2d_q(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor, b_zero: Optional[torch.Tensor], kernel_size,
+                   stride=1, padding=0, dilation=1, *, x_codes: bool = False, out_quant: Optional[OutQuant] = None, bits: int = 8,
+                   symmetric: bool = False, min_dev: Optional[torch.Tensor] = None, max_dev: Optional[torch.Tensor] = None,
+                   min_value=None, max_value=None, scale_f32: bool = False, b_packed: bool = False,
+                   bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``int_dwconv2d`` with stored activation codes at either end (dfq_int_dwconv2d_q): ``x_codes``
+    and ``out_quant`` as for ``int_conv2d_q`` -- the footprint's bytes are copied to LDS instead of
+    quantized, and a lane's four outputs go out as one word of codes.  With neither option the
+    result is ``int_dwconv2d``'s."""
+    return _dwconv2d(x, b_codes, b_scale, b_zero, kernel_size, stride, padding, dilation, bits, symmetric, min_dev, max_dev,
+                     min_value, max_value, scale_f32, b_packed, bias, out, _io_arg(out_quant, x_codes) or _lib.IntIo(), out_quant)
 
 
 def group_quant(w2d: torch.Tensor, bits: int, group: int, *, symmetric: bool = False, packed: bool = False):

@@ -1003,6 +1003,51 @@ typedef struct dfq_int_dwconv2d_desc {
 } dfq_int_dwconv2d_desc;
 int dfq_int_dwconv2d(const dfq_int_dwconv2d_desc* d, void* stream);
 
+/* ---- stored activation codes in and out of the four integer entries (no reference counterpart) ----
+ * dfq_int_gemm, dfq_int_linear, dfq_int_conv2d and dfq_int_dwconv2d with the two ends of an
+ * integer deployment: a store that writes the next layer's codes, and convolutions that read
+ * stored codes.  The descriptor is the old entry's; a dfq_int_io next to it says what changes.
+ * Input codes (x_codes, the convolutions only): d->x points to a contiguous NCHW tensor of
+ * bytes, uint8, or int8 when d->x_symmetric, 1-B aligned.  The descriptor's range (min_dev /
+ * max_dev / given_*, x_bits, x_symmetric, DFQ_SCALE_F32) names the grid the codes are on: sa and
+ * za are make_qparams' of it, what the in-kernel quantizer derives, and qa is the stored byte.  A
+ * byte above 2^x_bits - 1 is the caller's error and is not checked.  Nothing is quantized on the
+ * A side: a lane gathers its 16 taps as bytes (dfq_int_dwconv2d: the footprint's bytes are
+ * copied to LDS, words where a row's start allows).  Padding taps are absent from every sum, as
+ * in the old entries.
+ * Output codes (out_bits 2..8): the contract's out = (float)acc is computed exactly as in the old
+ * entry -- the same integers, the same fp64 steps in the same order, bias included -- and the byte
+ * stored in its place is dfq_fake_quant_given's q of it on the output range (out_min_dev[0] /
+ * out_max_dev[0], device floats read as exact doubles, or out_given_min / out_given_max;
+ * out_symmetric; out_flags DFQ_SCALE_F32 or 0):
+ *   q = rint(clamp((out + negmn) / s, qmin, qmax)),
+ * the byte dfq_quantize_tensor stores for out on that range, uint8, or int8 when out_symmetric.
+ * d->out then points to bytes, 1-B aligned: [M, N] with ldo counting bytes (gemm, linear), or
+ * contiguous [B, N, OH, OW] (the convolutions; a lane's four bytes go out as one 4-B store where
+ * they lie in one image and their address is 4-B aligned).  An activation needs no argument: on a
+ * range with min = 0 (and max <= 6) the quantizer's clamp is the ReLU (ReLU6).  So a chain of
+ * layers exchanges uint8 tensors and is bit for bit the old entries with dfq_fake_quant_given
+ * between them.  Group-wise B is not taken here.
+ * Checks: the old entry's (a byte tensor needs no alignment), then DFQ_ERR_INVALID for a NULL io,
+ * x_codes not 0 / 1 or set for gemm / linear (gemm reads codes already; linear on codes is gemm),
+ * out_bits outside {0, 2..8}, out_symmetric not 0 / 1, out_flags other than DFQ_SCALE_F32, a range
+ * pointer not 4-B aligned, and out_bits > 0 with no range: no device pointer and not
+ * out_given_max > out_given_min (each bound comes from its pointer where there is one).  With x_codes = 0 and out_bits = 0 the call is the old entry's. */
+typedef struct dfq_int_io {
+    int32_t      x_codes;        /* conv / dwconv only: d->x points to stored code bytes, not fp32 */
+    int32_t      out_bits;       /* 0: fp32 output; 2..8: d->out points to code bytes */
+    int32_t      out_symmetric;
+    int32_t      out_flags;      /* DFQ_SCALE_F32 or 0 */
+    const float* out_min_dev;    /* device floats, or NULL: out_given_min / out_given_max */
+    const float* out_max_dev;
+    double       out_given_min;
+    double       out_given_max;
+} dfq_int_io;
+int dfq_int_gemm_q(const dfq_int_gemm_desc* d, const dfq_int_io* io, void* stream);
+int dfq_int_linear_q(const dfq_int_linear_desc* d, const dfq_int_io* io, void* stream);
+int dfq_int_conv2d_q(const dfq_int_conv2d_desc* d, const dfq_int_io* io, void* stream);
+int dfq_int_dwconv2d_q(const dfq_int_dwconv2d_desc* d, const dfq_int_io* io, void* stream);
+
 /* ---- high-bias absorption (bias_absorption.py:147-197) ------------------
  * c = max(bn_b - N*bn_w, 0) (bn_* = the BN's fake_weight / fake_bias);
  * b2[o] += sum_i (sum_k W2[o,i,k]) * c[g*i2 + i];  b1 -= c;  bn_b -= c.
