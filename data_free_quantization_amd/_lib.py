@@ -44,6 +44,7 @@ EXPORTS = [
     "dfq_int_gemm", "dfq_int_linear", "dfq_int_conv2d", "dfq_int_dwconv2d",
     "dfq_int_gemm_grouped", "dfq_int_linear_grouped", "dfq_int_conv2d_grouped",
     "dfq_int_gemm_q", "dfq_int_linear_q", "dfq_int_conv2d_q", "dfq_int_dwconv2d_q",
+    "dfq_int_mbconv_q",
 ]
 #: entry points only the diagnostics library exports (include/dfq_diag.h)
 DIAG_EXPORTS = ["dfq_probe_stream", "dfq_probe_lds", "dfq_debug_timeline", "dfq_debug_ablate",
@@ -202,6 +203,27 @@ class IntIo(C.Structure):
     ]
 
 
+class IntMbconvLayer(C.Structure):
+    _fields_ = [("b_codes", C.c_void_p), ("b_scale", C.c_void_p), ("b_zero", C.c_void_p), ("bias", C.c_void_p),
+                ("b_signed", C.c_int32), ("flags", C.c_int32)]
+
+
+class IntMbconvQuant(C.Structure):
+    _fields_ = [("min_dev", C.c_void_p), ("max_dev", C.c_void_p), ("given_min", C.c_double), ("given_max", C.c_double),
+                ("bits", C.c_int32), ("symmetric", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class IntMbconvDesc(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("out", C.c_void_p),
+        ("expand", IntMbconvLayer), ("depthwise", IntMbconvLayer), ("project", IntMbconvLayer),
+        ("x_quant", IntMbconvQuant), ("hidden1", IntMbconvQuant), ("hidden2", IntMbconvQuant), ("out_quant", IntMbconvQuant),
+        ("B", C.c_int64), ("Cin", C.c_int64), ("H", C.c_int64), ("W", C.c_int64), ("Ch", C.c_int64), ("Cout", C.c_int64),
+        ("stride", C.c_int64), ("pad", C.c_int64),
+        ("flags", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 DFQ_BC_OP_EXPECT, DFQ_BC_OP_APPLY, DFQ_BC_OP_PROPAGATE, DFQ_BC_OP_COPY = 0, 1, 2, 3
 DFQ_BC_APPLY_VEC_SCRATCH = 1
 DFQ_BN_FOLD_ZERO_BIAS = 1
@@ -214,6 +236,7 @@ DFQ_MX_FP6_E2M3, DFQ_MX_FP6_E3M2 = 0x23, 0x32   # self-describing (exponent, man
 DFQ_MX_TASK_ELEMS, DFQ_MX_ESUM_TASK_ELEMS = 4096, 2048
 DFQ_INT_B_PACK4, DFQ_INT_B_PER_ROW, DFQ_INT_MAX_K = 0x1, 0x2, 32768
 DFQ_INT_DW_MAX_TAPS, DFQ_INT_DW_TILE_H, DFQ_INT_DW_TILE_W, DFQ_INT_DW_LDS_BYTES = 64, 32, 64, 16384
+DFQ_INT_MB_MAX_CIN, DFQ_INT_MB_MAX_COUT, DFQ_INT_MB_LDS_BYTES = 256, 320, 65536
 
 _LIB: Optional[C.CDLL] = None
 
@@ -313,6 +336,7 @@ def load(path: Optional[os.PathLike] = None) -> C.CDLL:
         "dfq_int_linear_q": ([C.POINTER(IntLinearDesc), C.POINTER(IntIo), P], C.c_int),
         "dfq_int_conv2d_q": ([C.POINTER(IntConv2dDesc), C.POINTER(IntIo), P], C.c_int),
         "dfq_int_dwconv2d_q": ([C.POINTER(IntDwConv2dDesc), C.POINTER(IntIo), P], C.c_int),
+        "dfq_int_mbconv_q": ([C.POINTER(IntMbconvDesc), P], C.c_int),
     }
     diag = {
         "dfq_probe_stream": ([P, P, P, P, I64, I32, P], C.c_int),

@@ -14,8 +14,9 @@ and ``int_conv2d_grouped`` take group-wise weight parameters, a scale and zero p
 elements of a weight row (``group_quant`` writes them; tests/int_group_cases.py).  ``out_quant``
 (``int_gemm``, ``int_linear``) and ``int_conv2d_q`` / ``int_dwconv2d_q`` store the next layer's
 activation codes instead of fp32, and the two convolutions read such codes (``x_codes``), so a
-run of layers exchanges uint8 tensors (tests/int_io_cases.py).  There is no CPU fallback: CPU
-tensors raise."""
+run of layers exchanges uint8 tensors (tests/int_io_cases.py); ``int_mbconv_q`` runs MobileNetV2's
+expand -> depthwise -> project block on such codes in one launch, the hidden tensors in LDS.
+There is no CPU fallback: CPU tensors raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -493,6 +494,79 @@ def int_dwconv2d_q(x: torch.Tensor, b_codes: torch.Tensor, b_scale: torch.Tensor
     result is ``int_dwconv2d``'s."""
     return _dwconv2d(x, b_codes, b_scale, b_zero, kernel_size, stride, padding, dilation, bits, symmetric, min_dev, max_dev,
                      min_value, max_value, scale_f32, b_packed, bias, out, _io_arg(out_quant, x_codes) or _lib.IntIo(), out_quant)
+
+
+MB_MAX_CIN, MB_MAX_COUT = _lib.DFQ_INT_MB_MAX_CIN, _lib.DFQ_INT_MB_MAX_COUT
+
+
+def _mb_quant(q, name: str, oq: OutQuant, tensors: list) -> None:
+    """A grid of ``int_mbconv_q`` as the descriptor takes it: ``_io_arg``'s checks of an ``OutQuant``."""
+    io = _io_arg(oq, False)
+    q.min_dev, q.max_dev, q.given_min, q.given_max, q.flags = io.out_min_dev, io.out_max_dev, io.out_given_min, io.out_given_max, io.out_flags
+    q.bits, q.symmetric = io.out_bits, io.out_symmetric
+    tensors += [oq.min_dev, oq.max_dev]
+
+
+def int_mbconv_q(x_codes: torch.Tensor, expand, depthwise, project, *, stride: int = 1, padding: int = 1, bits: int = 8,
+                 symmetric: bool = False, min_dev: Optional[torch.Tensor] = None, max_dev: Optional[torch.Tensor] = None,
+                 min_value=None, max_value=None, scale_f32: bool = False, hidden1: OutQuant, hidden2: OutQuant,
+                 out_quant: Optional[OutQuant] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """MobileNetV2's inverted-residual block -- 1 x 1 expand -> depthwise 3 x 3 -> 1 x 1 project -- on
+    stored codes in one launch, the two hidden tensors kept in LDS (dfq_int_mbconv_q).
+
+    ``x_codes``: a contiguous NCHW tensor of codes -- uint8, or int8 when ``symmetric``, else
+    TypeError -- on the grid the range keywords and ``bits`` name, as ``int_conv2d_q(x_codes=True)``
+    takes it.  ``expand``, ``depthwise``, ``project``: each a ``(b_codes, b_scale, b_zero, bias)``
+    tuple as the other entries take them, of shapes [Ch, Cin], [Ch, 9] and [Cout, Ch]; uint8 or int8
+    bytes, scale / zero per tensor or per row, ``b_zero`` and ``bias`` may be None.  ``hidden1`` /
+    ``hidden2`` (``OutQuant``): the grids of the expand's and the depthwise's outputs; on [0, 6] the
+    clamp is the ReLU6.  ``stride`` 1 or 2, ``padding`` 0 or 1, both axes.  The result is bit for bit
+    ``int_conv2d_q(x, *expand, 1, x_codes=True, out_quant=hidden1)`` -> ``int_dwconv2d_q(c1,
+    *depthwise, 3, stride, padding, x_codes=True, out_quant=hidden2, <hidden1's grid>)`` ->
+    ``int_conv2d_q(c2, *project, 1, x_codes=True, out_quant=out_quant, <hidden2's grid>)``: fp32
+    [B, Cout, OH, OW], or under ``out_quant`` its code bytes; ``out``, if passed, is such a tensor.
+    Cin <= ``MB_MAX_CIN``, Cout <= ``MB_MAX_COUT`` and Ch <= ``MAX_K``, else NotImplementedError.  The
+    residual add is the caller's.  Counts 1 in ``LINEAR_CALLS``.  Asynchronous on the current
+    stream; there is no CPU fallback."""
+    global LINEAR_CALLS
+    bits = _x_arg(x_codes, bits, symmetric, True)
+    stride, padding = int(stride), int(padding)
+    if stride < 1 or padding < 0:
+        raise ValueError("stride must be >= 1 and padding >= 0")
+    if x_codes.dim() != 4 or not x_codes.is_contiguous() or x_codes.numel() == 0:
+        raise ValueError("x_codes must be a contiguous [B, C, H, W] tensor, got %s with strides %s" % (tuple(x_codes.shape), tuple(x_codes.stride())))
+    B, Cin, H, W = x_codes.shape
+    d = _lib.IntMbconvDesc()
+    dev, tensors, rows = x_codes.device, [min_dev, max_dev], []
+    d.x_quant.min_dev, d.x_quant.max_dev, d.x_quant.given_min, d.x_quant.given_max, d.x_quant.flags = _range_fields(min_dev, max_dev, min_value, max_value, scale_f32)
+    d.x_quant.bits, d.x_quant.symmetric = bits, int(bool(symmetric))
+    for name, layer, K in (("expand", expand, Cin), ("depthwise", depthwise, 9), ("project", project, None)):
+        if not isinstance(layer, (tuple, list)) or len(layer) != 4:
+            raise TypeError("%s: a (b_codes, b_scale, b_zero, bias) tuple" % name)
+        b_codes, b_scale, b_zero, bias = layer
+        N = _b_args(getattr(d, name), b_codes, b_scale, b_zero, _k_arg(K if K is not None else rows[0]), False)
+        if name == "depthwise" and N != rows[0]:
+            raise ValueError("depthwise holds %d rows of 9, the expand layer %d channels" % (N, rows[0]))
+        _bias_dev_args("int_mbconv_q", N, dev, bias, (b_codes, b_scale, b_zero))
+        getattr(d, name).bias = bias.data_ptr() if bias is not None else None
+        rows.append(N)
+    Ch, _, Cout = rows
+    for name, oq in (("hidden1", hidden1), ("hidden2", hidden2)):
+        if not isinstance(oq, OutQuant):
+            raise TypeError(name + ": an intmm.OutQuant")
+        _mb_quant(getattr(d, name), name, oq, tensors)
+    if out_quant is not None:
+        _mb_quant(d.out_quant, "out_quant", out_quant, tensors)
+    OH, OW = mx.conv_out_size(H, 3, stride, padding, 1), mx.conv_out_size(W, 3, stride, padding, 1)
+    if OH < 1 or OW < 1:
+        raise ValueError("the 3 x 3 kernel does not fit the padded input %s" % ((H + 2 * padding, W + 2 * padding),))
+    out = _conv_out("int_mbconv_q", (B, Cout, OH, OW), out, out_quant, dev)
+    _bias_dev_args("int_mbconv_q", Cout, dev, None, (*tensors, out))
+    d.x, d.out = x_codes.data_ptr(), out.data_ptr()
+    d.B, d.Cin, d.H, d.W, d.Ch, d.Cout, d.stride, d.pad = B, Cin, H, W, Ch, Cout, stride, padding
+    _lib.check(_lib.load().dfq_int_mbconv_q(C.byref(d), _lib.raw_stream(dev)), "dfq_int_mbconv_q", ValueError)
+    LINEAR_CALLS += 1
+    return out
 
 
 def group_quant(w2d: torch.Tensor, bits: int, group: int, *, symmetric: bool = False, packed: bool = False):

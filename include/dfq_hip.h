@@ -1048,6 +1048,82 @@ int dfq_int_linear_q(const dfq_int_linear_desc* d, const dfq_int_io* io, void* s
 int dfq_int_conv2d_q(const dfq_int_conv2d_desc* d, const dfq_int_io* io, void* stream);
 int dfq_int_dwconv2d_q(const dfq_int_dwconv2d_desc* d, const dfq_int_io* io, void* stream);
 
+/* ---- integer inverted-residual block in one launch (no reference counterpart) ----
+ * MobileNetV2's expand 1x1 -> depthwise 3x3 -> project 1x1 on stored codes, the two hidden
+ * tensors kept in LDS as code bytes.  For x a contiguous NCHW tensor of codes on the grid x_quant
+ * names (uint8, or int8 when x_quant.symmetric; 1-B aligned) the result is bit for bit
+ *   c1  = dfq_int_conv2d_q  (x,  expand,    1x1,                  x_codes, out codes on hidden1)
+ *   c2  = dfq_int_dwconv2d_q(c1, depthwise, 3x3, stride, pad,     x_codes on hidden1, out codes on hidden2)
+ *   out = dfq_int_conv2d_q  (c2, project,   1x1,                  x_codes on hidden2, out_quant)
+ * with everything those carry: exact integer sums, the five fp64 steps in their order per layer,
+ * a depthwise tap in padding absent from every sum (a hidden pixel outside the image does not
+ * exist -- it is not the expand layer applied to a zero input), every requantization
+ * dfq_fake_quant_given's code, and the final store fp32 [B, Cout, OH, OW] or, with
+ * out_quant.bits 2..8, code bytes.  c1 and c2 never reach global memory.
+ * Weights: expand [Ch, Cin], depthwise [Ch, 9], project [Cout, Ch] bytes (uint8, or int8 with
+ * b_signed), scale / zero per tensor or per row (DFQ_INT_B_PER_ROW in the layer's flags), zero
+ * and bias optional.
+ * A workgroup owns one image, one tile of at most 8 x 8 outputs (4 x 8 at stride 2) and all Cout
+ * channels: it stages the tile's input footprint as [pixel][Cin] bytes in LDS, then for each 64
+ * hidden channels runs the expand on the i8 matrix instruction into LDS code planes, the depthwise
+ * on the packed 8-bit dot instruction into the project's A tile in LDS, and accumulates the
+ * project in registers across all chunks.  No workspace, no atomics, no split of any sum: the
+ * same bits from run to run.  Asynchronous on `stream`, no host wait.
+ * Checked on the host before any device call, in the siblings' order: DFQ_ERR_INVALID for a NULL
+ * d, x, out, b_codes or b_scale, unknown flags, non-zero reserved, b_signed or symmetric not
+ * 0 / 1, bits of x_quant, hidden1 or hidden2 outside 2..8, out_quant.bits outside {0, 2..8}, a
+ * quantizer with neither a device pointer nor given_max > given_min (out_quant: only when its
+ * bits > 0), an extent (B, Cin, H, W, Ch, Cout) or stride < 1, pad < 0, any of these above 2^28,
+ * Cin * H * W or Cout * OH * OW at or above 2^31, B * OH * OW above 2^31, a scale, zero, bias or
+ * range pointer not 4-B aligned, a b_codes not 16-B aligned, an fp32 out not 4-B aligned;
+ * DFQ_ERR_SHAPE when OH or OW comes out < 1; DFQ_ERR_UNSUPPORTED for a stride above 2, a pad
+ * above 1, DFQ_INT_B_PACK4 on a layer, Cin > DFQ_INT_MB_MAX_CIN, Cout > DFQ_INT_MB_MAX_COUT,
+ * Ch > DFQ_INT_MAX_K, LDS beyond DFQ_INT_MB_LDS_BYTES, a grid beyond int32.  Group-wise weights
+ * have no field here. */
+#define DFQ_INT_MB_MAX_CIN    256    /* the expand's K: four steps of the matrix instruction held in registers */
+#define DFQ_INT_MB_MAX_COUT   320    /* the project's accumulators: 64 x 320 int32 are 80 registers a lane */
+#define DFQ_INT_MB_LDS_BYTES  65536  /* the LDS of a workgroup */
+typedef struct dfq_int_mbconv_layer {
+    const void*  b_codes;   /* [N, K] bytes, 16-B aligned */
+    const float* b_scale;   /* device, 1 or N values */
+    const float* b_zero;    /* device, 1 or N values, or NULL (0) */
+    const float* bias;      /* [N] or NULL */
+    int32_t      b_signed;
+    int32_t      flags;     /* DFQ_INT_B_PER_ROW */
+} dfq_int_mbconv_layer;
+typedef struct dfq_int_mbconv_quant {   /* a grid: dfq_fake_quant_given's arguments */
+    const float* min_dev;   /* device floats, or NULL: given_min / given_max */
+    const float* max_dev;
+    double       given_min;
+    double       given_max;
+    int32_t      bits;      /* 2..8 (out_quant: 0 for an fp32 output) */
+    int32_t      symmetric;
+    int32_t      flags;     /* DFQ_SCALE_F32 or 0 */
+    int32_t      reserved;  /* 0 */
+} dfq_int_mbconv_quant;
+typedef struct dfq_int_mbconv_desc {
+    const void*  x;         /* code bytes [B, Cin, H, W], contiguous */
+    void*        out;       /* fp32, or code bytes, [B, Cout, OH, OW], contiguous */
+    dfq_int_mbconv_layer expand;      /* [Ch, Cin] */
+    dfq_int_mbconv_layer depthwise;   /* [Ch, 9] */
+    dfq_int_mbconv_layer project;     /* [Cout, Ch] */
+    dfq_int_mbconv_quant x_quant;     /* the grid x's codes are on */
+    dfq_int_mbconv_quant hidden1;     /* the expand's output grid */
+    dfq_int_mbconv_quant hidden2;     /* the depthwise's output grid */
+    dfq_int_mbconv_quant out_quant;   /* bits 0: fp32 output */
+    int64_t      B;
+    int64_t      Cin;
+    int64_t      H;
+    int64_t      W;
+    int64_t      Ch;
+    int64_t      Cout;
+    int64_t      stride;    /* 1 or 2, both axes */
+    int64_t      pad;       /* 0 or 1, both axes */
+    int32_t      flags;     /* 0 */
+    int32_t      reserved;  /* 0 */
+} dfq_int_mbconv_desc;
+int dfq_int_mbconv_q(const dfq_int_mbconv_desc* d, void* stream);
+
 /* ---- high-bias absorption (bias_absorption.py:147-197) ------------------
  * c = max(bn_b - N*bn_w, 0) (bn_* = the BN's fake_weight / fake_bias);
  * b2[o] += sum_i (sum_k W2[o,i,k]) * c[g*i2 + i];  b1 -= c;  bn_b -= c.
