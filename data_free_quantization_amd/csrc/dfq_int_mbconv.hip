@@ -26,6 +26,9 @@
 //                 rows are four consecutive ow -- one 16-B / 4-B store where all exist (and the
 //                 byte address allows), else element by element.
 // CT: column tiles of a wave in the project (Cout <= 64 CT).  OC: the output is code bytes.
+// RES (dfq_int_mbconv_res_q; stride 1, pad 1, Cin == Cout): between the epilogue's value and its
+// store, the value becomes dq_P(its code on proj_quant) + dq_X(x's code at the pixel) -- the
+// shortcut's byte is the one step 1 staged in xs (mb_res_fr), which no chunk overwrites.
 // Two barriers a chunk: hid and wts are written in (a) and read in (b); pa is written in (b) and
 // read in (c); the next chunk's (a) touches neither pa nor xs.  No scratch, no atomics, no workspace.
 #include "dfq_int_mm_sources.h"
@@ -47,6 +50,7 @@ struct MbArgs {
     void* out;
     MbLayer e, d, p;
     IgOutQ qx, q1, q2, qo;    // the grids of x, hidden1, hidden2 and the output
+    IgOutQ qp;                // RES: the grid of the project's output, the add's first operand
     MbGeom g;
 };
 
@@ -86,7 +90,7 @@ __device__ __forceinline__ ig_v4i mb_b_frag(const uint8_t* b, int64_t row, int64
     return IgBytesB<false>::operand(f, xm, ig_lane_valid(row, rows, ig_lane_k0(step, lane), K));
 }
 
-template <int CT, bool OC>
+template <int CT, bool OC, bool RES>
 __global__ __launch_bounds__(kThreads) void int_mbconv_kernel(const MbArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t mb_lds[];
     uint8_t* lds = mb_lds;
@@ -240,8 +244,9 @@ __global__ __launch_bounds__(kThreads) void int_mbconv_kernel(const MbArgs a) {
     }
 
     // 3. the project's epilogue
-    IgAParams po;
+    IgAParams po, pp;
     if constexpr (OC) po = ig_out_params(a.qo);
+    if constexpr (RES) pp = ig_out_params(a.qp);
 #pragma unroll
     for (int j = 0; j < CT; ++j) {
         const int32_t tile = j * kMbWaves + wave;
@@ -259,6 +264,14 @@ __global__ __launch_bounds__(kThreads) void int_mbconv_kernel(const MbArgs a) {
             for (int r = 0; r < 4; ++r) {
                 v[r] = mb_value(f, acc[i][j][r], pra[i][r], prb[j][r], p2.off, ob_p, g.Ch);
                 on[r] = col_on && mb_tp_on(g, blk, tp0 + r);
+            }
+            if constexpr (RES) {   // v := dq_P(the project's code) + dq_X(x's code at the pixel, from xs)
+                const uint32_t pc = ig_codes4(v, pp);   // every lane of the wave
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int8_t xc = (int8_t)lds[mb_xs_byte(g, mb_res_fr(g, tp0 + r, on[r]), (int32_t)n)];
+                    v[r] = ig_code_value((int8_t)((pc >> (8 * r)) ^ pp.xm), pp) + ig_code_value(xc, px);
+                }
             }
             const int64_t o = mb_out_offset(g, blk.b, n, blk.oh0 + (tp0 >> 3), blk.ow0 + (tp0 & 7));
             const bool all_on = on[0] && on[1] && on[2] && on[3];
@@ -294,24 +307,18 @@ IgOutQ mb_quant(const dfq_int_mbconv_quant& q) {
     return IgOutQ{q.min_dev, q.max_dev, q.given_min, q.given_max, q.bits, q.symmetric, q.flags};
 }
 
-template <int CT>
+template <int CT, bool RES>
 void mb_launch(const MbArgs& a, bool codes, int64_t grid, hipStream_t s) {
     const dim3 blocks((unsigned)grid), threads(kThreads);
-    if (codes) hipLaunchKernelGGL((int_mbconv_kernel<CT, true>), blocks, threads, (size_t)a.g.lds_bytes, s, a);
-    else hipLaunchKernelGGL((int_mbconv_kernel<CT, false>), blocks, threads, (size_t)a.g.lds_bytes, s, a);
+    if (codes) hipLaunchKernelGGL((int_mbconv_kernel<CT, true, RES>), blocks, threads, (size_t)a.g.lds_bytes, s, a);
+    else hipLaunchKernelGGL((int_mbconv_kernel<CT, false, RES>), blocks, threads, (size_t)a.g.lds_bytes, s, a);
 }
 
-}  // namespace
-}  // namespace dfq
-
-using namespace dfq;
-
-static_assert(DFQ_INT_MB_MAX_COUT <= 5 * kMbWaves * 16, "the widest project fits five column tiles a wave");
-
-extern "C" int dfq_int_mbconv_q(const dfq_int_mbconv_desc* d, void* stream) {
+// Both entries: r is null for dfq_int_mbconv_q.
+int mb_run(const dfq_int_mbconv_desc* d, const dfq_int_mbconv_res* r, bool res, void* stream) {
     MbArgs a{};
     int64_t grid = 0;
-    const int rc = mb_check(d, a.g, grid);
+    const int rc = res ? mb_res_check(d, r, a.g, grid) : mb_check(d, a.g, grid);
     if (rc != DFQ_OK) return rc;
     a.x = static_cast<const uint8_t*>(d->x);
     a.out = d->out;
@@ -322,10 +329,26 @@ extern "C" int dfq_int_mbconv_q(const dfq_int_mbconv_desc* d, void* stream) {
     a.q1 = mb_quant(d->hidden1);
     a.q2 = mb_quant(d->hidden2);
     a.qo = mb_quant(d->out_quant);
+    if (res) a.qp = mb_quant(r->proj_quant);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool codes = d->out_quant.bits > 0;
-    if (a.g.nt <= 2 * kMbWaves) mb_launch<2>(a, codes, grid, s);
-    else mb_launch<5>(a, codes, grid, s);
+    const bool codes = d->out_quant.bits > 0, wide = a.g.nt > 2 * kMbWaves;
+    if (res && wide) mb_launch<5, true>(a, codes, grid, s);
+    else if (res) mb_launch<2, true>(a, codes, grid, s);
+    else if (wide) mb_launch<5, false>(a, codes, grid, s);
+    else mb_launch<2, false>(a, codes, grid, s);
     DFQ_LAUNCH_CHECK();
     return DFQ_OK;
+}
+
+}  // namespace
+}  // namespace dfq
+
+using namespace dfq;
+
+static_assert(DFQ_INT_MB_MAX_COUT <= 5 * kMbWaves * 16, "the widest project fits five column tiles a wave");
+
+extern "C" int dfq_int_mbconv_q(const dfq_int_mbconv_desc* d, void* stream) { return mb_run(d, nullptr, false, stream); }
+
+extern "C" int dfq_int_mbconv_res_q(const dfq_int_mbconv_desc* d, const dfq_int_mbconv_res* r, void* stream) {
+    return mb_run(d, r, true, stream);
 }

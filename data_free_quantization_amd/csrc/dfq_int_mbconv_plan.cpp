@@ -13,16 +13,16 @@ int mb_check_layer(const dfq_int_mbconv_layer& l) {
     if (l.b_signed != 0 && l.b_signed != 1) return DFQ_ERR_INVALID;
     return DFQ_OK;
 }
-int mb_check_quant(const dfq_int_mbconv_quant& q, bool optional) {
-    if (q.reserved != 0 || (q.flags & ~DFQ_SCALE_F32) != 0) return DFQ_ERR_INVALID;
-    if (q.symmetric != 0 && q.symmetric != 1) return DFQ_ERR_INVALID;
-    if (optional && q.bits == 0) return DFQ_OK;
-    if (q.bits < 2 || q.bits > 8) return DFQ_ERR_INVALID;
-    if (!q.min_dev && !q.max_dev && !(q.given_max > q.given_min)) return DFQ_ERR_INVALID;
+}  // namespace
+
+int mb_res_check(const dfq_int_mbconv_desc* d, const dfq_int_mbconv_res* r, MbGeom& g, int64_t& grid) {
+    if (int rc = mb_check(d, g, grid)) return rc;
+    if (!r || r->flags != 0 || r->reserved != 0) return DFQ_ERR_INVALID;
+    if (int rc = mb_check_quant(r->proj_quant, false)) return rc;
+    if (!mb_quant_aligned(r->proj_quant)) return DFQ_ERR_INVALID;
+    if (d->stride != 1 || d->pad != 1 || d->Cin != d->Cout) return DFQ_ERR_SHAPE;   // x and out: one shape
     return DFQ_OK;
 }
-
-}  // namespace
 
 int mb_check(const dfq_int_mbconv_desc* d, MbGeom& g, int64_t& grid) {
     g = MbGeom{};

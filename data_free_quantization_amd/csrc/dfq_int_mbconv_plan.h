@@ -134,8 +134,30 @@ DFQ_HOST_DEVICE inline int64_t mb_out_offset(const MbGeom& g, int32_t b, int64_t
     return ((int64_t)b * g.Cout + n) * g.OHW + (int64_t)oh * g.OW + ow;
 }
 
+// ---- the residual (dfq_int_mbconv_res_q): stride 1, pad 1, Cin == Cout ----
+// The footprint row that holds x at tile pixel tp: the footprint starts one pixel above and left
+// of the tile.  Row 0 for a pixel that is off (its value is never stored).
+DFQ_HOST_DEVICE inline int32_t mb_res_fr(const MbGeom& g, int32_t tp, bool on) {
+    return on ? ((tp >> 3) + 1) * g.fw + (tp & 7) + 1 : 0;
+}
+
+// A grid's checks (dfq_int_mbconv_quant): its fields, then its range pointers' alignment.
+inline int mb_check_quant(const dfq_int_mbconv_quant& q, bool optional) {
+    if (q.reserved != 0 || (q.flags & ~DFQ_SCALE_F32) != 0) return DFQ_ERR_INVALID;
+    if (q.symmetric != 0 && q.symmetric != 1) return DFQ_ERR_INVALID;
+    if (optional && q.bits == 0) return DFQ_OK;
+    if (q.bits < 2 || q.bits > 8) return DFQ_ERR_INVALID;
+    if (!q.min_dev && !q.max_dev && !(q.given_max > q.given_min)) return DFQ_ERR_INVALID;
+    return DFQ_OK;
+}
+inline bool mb_quant_aligned(const dfq_int_mbconv_quant& q) {
+    return reinterpret_cast<uintptr_t>(q.min_dev) % 4 == 0 && reinterpret_cast<uintptr_t>(q.max_dev) % 4 == 0;
+}
+
 // dfq_int_mbconv_q's argument checks (no device call): DFQ_OK with the geometry and the grid, or
 // the error.
 int mb_check(const dfq_int_mbconv_desc* d, MbGeom& g, int64_t& grid);
+// dfq_int_mbconv_res_q's: mb_check, then the residual struct's and the shapes the add needs.
+int mb_res_check(const dfq_int_mbconv_desc* d, const dfq_int_mbconv_res* r, MbGeom& g, int64_t& grid);
 
 }  // namespace dfq

@@ -59,4 +59,13 @@ __device__ __forceinline__ uint32_t ig_codes4(const float* x, const IgAParams& p
     return w;
 }
 
+// The fp32 value a stored code stands for on its grid -- what dfq_fake_quant_given returns for
+// it: qdq_finish's product and sum, each rounded once.  sb: the code's byte in the signed domain
+// (the stored byte ^ p.xm), as the matrix kernels' operands hold it.
+__device__ __forceinline__ float ig_code_value(int8_t sb, const IgAParams& p) {
+    const float q = (float)((int)sb + p.off);
+    const float y = q * p.q.s;
+    return y + p.q.mn;
+}
+
 }  // namespace dfq

@@ -15,7 +15,8 @@ elements of a weight row (``group_quant`` writes them; tests/int_group_cases.py)
 (``int_gemm``, ``int_linear``) and ``int_conv2d_q`` / ``int_dwconv2d_q`` store the next layer's
 activation codes instead of fp32, and the two convolutions read such codes (``x_codes``), so a
 run of layers exchanges uint8 tensors (tests/int_io_cases.py); ``int_mbconv_q`` runs MobileNetV2's
-expand -> depthwise -> project block on such codes in one launch, the hidden tensors in LDS.
+expand -> depthwise -> project block on such codes in one launch, the hidden tensors in LDS, with the block's residual add in its
+epilogue under ``residual``; ``int_add_q`` adds two code tensors.
 There is no CPU fallback: CPU tensors raise."""
 from __future__ import annotations
 
@@ -510,7 +511,8 @@ def _mb_quant(q, name: str, oq: OutQuant, tensors: list) -> None:
 def int_mbconv_q(x_codes: torch.Tensor, expand, depthwise, project, *, stride: int = 1, padding: int = 1, bits: int = 8,
                  symmetric: bool = False, min_dev: Optional[torch.Tensor] = None, max_dev: Optional[torch.Tensor] = None,
                  min_value=None, max_value=None, scale_f32: bool = False, hidden1: OutQuant, hidden2: OutQuant,
-                 out_quant: Optional[OutQuant] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 out_quant: Optional[OutQuant] = None, out: Optional[torch.Tensor] = None,
+                 residual: Optional[OutQuant] = None) -> torch.Tensor:
     """MobileNetV2's inverted-residual block -- 1 x 1 expand -> depthwise 3 x 3 -> 1 x 1 project -- on
     stored codes in one launch, the two hidden tensors kept in LDS (dfq_int_mbconv_q).
 
@@ -525,10 +527,19 @@ def int_mbconv_q(x_codes: torch.Tensor, expand, depthwise, project, *, stride: i
     *depthwise, 3, stride, padding, x_codes=True, out_quant=hidden2, <hidden1's grid>)`` ->
     ``int_conv2d_q(c2, *project, 1, x_codes=True, out_quant=out_quant, <hidden2's grid>)``: fp32
     [B, Cout, OH, OW], or under ``out_quant`` its code bytes; ``out``, if passed, is such a tensor.
-    Cin <= ``MB_MAX_CIN``, Cout <= ``MB_MAX_COUT`` and Ch <= ``MAX_K``, else NotImplementedError.  The
-    residual add is the caller's.  Counts 1 in ``LINEAR_CALLS``.  Asynchronous on the current
-    stream; there is no CPU fallback."""
+    Cin <= ``MB_MAX_CIN``, Cout <= ``MB_MAX_COUT`` and Ch <= ``MAX_K``, else NotImplementedError.
+
+    ``residual`` (an ``OutQuant``; dfq_int_mbconv_res_q): the block's ``x +
+    project(...)`` in the same launch.  ``residual`` is the grid of the project's output, and the
+    result is bit for bit ``int_add_q(int_mbconv_q(..., out_quant=residual), residual, x_codes,
+    <x's grid>, out_quant=out_quant)``: the shortcut's codes come from the footprint the kernel
+    already holds in LDS, the project's codes never reach memory.  Needs ``stride`` 1, ``padding`` 1
+    and Cin == Cout, else ValueError.  With None the call is dfq_int_mbconv_q's.
+
+    Counts 1 in ``LINEAR_CALLS``.  Asynchronous on the current stream; there is no CPU fallback."""
     global LINEAR_CALLS
+    if residual is not None and not isinstance(residual, OutQuant):
+        raise TypeError("residual: an intmm.OutQuant, the grid of the project's output")
     bits = _x_arg(x_codes, bits, symmetric, True)
     stride, padding = int(stride), int(padding)
     if stride < 1 or padding < 0:
@@ -557,6 +568,10 @@ def int_mbconv_q(x_codes: torch.Tensor, expand, depthwise, project, *, stride: i
         _mb_quant(getattr(d, name), name, oq, tensors)
     if out_quant is not None:
         _mb_quant(d.out_quant, "out_quant", out_quant, tensors)
+    res = None
+    if residual is not None:
+        res = _lib.IntMbconvRes()
+        _mb_quant(res.proj_quant, "residual", residual, tensors)
     OH, OW = mx.conv_out_size(H, 3, stride, padding, 1), mx.conv_out_size(W, 3, stride, padding, 1)
     if OH < 1 or OW < 1:
         raise ValueError("the 3 x 3 kernel does not fit the padded input %s" % ((H + 2 * padding, W + 2 * padding),))
@@ -564,8 +579,62 @@ def int_mbconv_q(x_codes: torch.Tensor, expand, depthwise, project, *, stride: i
     _bias_dev_args("int_mbconv_q", Cout, dev, None, (*tensors, out))
     d.x, d.out = x_codes.data_ptr(), out.data_ptr()
     d.B, d.Cin, d.H, d.W, d.Ch, d.Cout, d.stride, d.pad = B, Cin, H, W, Ch, Cout, stride, padding
-    _lib.check(_lib.load().dfq_int_mbconv_q(C.byref(d), _lib.raw_stream(dev)), "dfq_int_mbconv_q", ValueError)
+    if res is None:
+        _lib.check(_lib.load().dfq_int_mbconv_q(C.byref(d), _lib.raw_stream(dev)), "dfq_int_mbconv_q", ValueError)
+    else:
+        _lib.check(_lib.load().dfq_int_mbconv_res_q(C.byref(d), C.byref(res), _lib.raw_stream(dev)), "dfq_int_mbconv_res_q", ValueError)
     LINEAR_CALLS += 1
+    return out
+
+
+def _add_operand(name: str, codes, quant, q, tensors: list) -> None:
+    """An operand of ``int_add_q`` before its device is looked at: its grid's checks (``_mb_quant``) and, as ``_x_arg``, the dtype
+    the grid's ``symmetric`` names."""
+    if not isinstance(quant, OutQuant):
+        raise TypeError(name + "_quant: an intmm.OutQuant")
+    _mb_quant(q, name + "_quant", quant, tensors)
+    if not isinstance(codes, torch.Tensor):
+        raise TypeError("%s_codes: a uint8 or int8 tensor on the GPU" % name)
+    if codes.dtype != _code_dtype(quant.symmetric):
+        raise TypeError("%s_codes: stored codes are %s when symmetric=%s, got %s" % (name, _code_dtype(quant.symmetric), bool(quant.symmetric), codes.dtype))
+
+
+def int_add_q(a_codes: torch.Tensor, a_quant: OutQuant, b_codes: torch.Tensor, b_quant: OutQuant, *,
+              out_quant: Optional[OutQuant] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The sum of two tensors of stored codes in one launch (dfq_int_add_q): a
+    residual add that stays on bytes.  ``a_codes`` / ``b_codes``: contiguous tensors of one shape
+    on the GPU, uint8, or int8 when their grid (``a_quant`` / ``b_quant``, each an ``OutQuant``) is
+    symmetric, else TypeError; any byte address is taken (a slice such as ``flat[1:]`` gives the
+    same bits, more slowly).  With v the fp32 value ``fake_quant_given`` returns for a code on its
+    grid, the result is ``va + vb`` in fp32 -- or, under ``out_quant``, ``fake_quant_given``'s code
+    byte of that sum on ``out_quant``'s range; on a range with min = 0 the clamp is the ReLU of an
+    ``add_relu``.  No operand is requantized onto a second grid.  ``out``, if passed, is a
+    contiguous tensor of that shape and type.  Asynchronous on the current stream; there is no CPU
+    fallback."""
+    d = _lib.IntAddDesc()
+    tensors: list = []
+    _add_operand("a", a_codes, a_quant, d.a_quant, tensors)
+    _add_operand("b", b_codes, b_quant, d.b_quant, tensors)
+    if a_codes.shape != b_codes.shape:
+        raise ValueError("a_codes %s and b_codes %s must have one shape" % (tuple(a_codes.shape), tuple(b_codes.shape)))
+    for name, codes in (("a_codes", a_codes), ("b_codes", b_codes)):
+        _on_gpu(name, codes, "a uint8 or int8 tensor")
+        if not codes.is_contiguous() or codes.numel() == 0:
+            raise ValueError("%s must be a non-empty contiguous tensor, got %s with strides %s" % (name, tuple(codes.shape), tuple(codes.stride())))
+    if out_quant is not None:
+        _mb_quant(d.out_quant, "out_quant", out_quant, tensors)
+    dev, shape = a_codes.device, tuple(a_codes.shape)
+    if out_quant is not None:
+        out = _code_out("int_add_q", shape, out, out_quant, dev)
+    elif out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32:
+        raise TypeError("out: float32 on the GPU")
+    elif tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError("out must be a contiguous %s tensor" % (list(shape),))
+    _bias_dev_args("int_add_q", 0, dev, None, (*tensors, b_codes, out))
+    d.a, d.b, d.out, d.n = a_codes.data_ptr(), b_codes.data_ptr(), out.data_ptr(), a_codes.numel()
+    _lib.check(_lib.load().dfq_int_add_q(C.byref(d), _lib.raw_stream(dev)), "dfq_int_add_q", ValueError)
     return out
 
 

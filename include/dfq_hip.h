@@ -1124,6 +1124,59 @@ typedef struct dfq_int_mbconv_desc {
 } dfq_int_mbconv_desc;
 int dfq_int_mbconv_q(const dfq_int_mbconv_desc* d, void* stream);
 
+/* ---- the residual add on stored codes (no reference counterpart) ----
+ * dfq_int_add_q: the sum of two code tensors in one launch.  a and b are contiguous tensors of n
+ * code bytes on the grids a_quant and b_quant (uint8, or int8 when the grid is symmetric; 1-B
+ * aligned).  With dq the fp32 value dfq_fake_quant_given returns for a code on its grid --
+ * fl32(fl32(q * s) + mn), s and mn make_qparams' of the range --
+ *   va = dq_A(a[i]);  vb = dq_B(b[i]);  y = fl32(va + vb)
+ *   out[i] = y                    (out_quant.bits == 0: fp32, 4-B aligned)
+ *   out[i] = q_O(y)               (bits 2..8: dfq_fake_quant_given's code byte of y on out_quant)
+ * No operand is requantized onto a second grid: a stored tensor has one grid.  The ReLU of an
+ * add_relu needs no argument: it is the clamp of a range with min = 0.  Every step is elementwise,
+ * so the result is the statement's bits whatever the split.
+ * A lane owns 16 consecutive elements, counted from a's first 16-B boundary: one 16-B load from
+ * each operand, four words of codes, one 16-B store (fp32: four 16-B stores), grid-stride.  An
+ * operand whose base disagrees with a's mod 16 goes by 4-B words or bytes; the elements before
+ * the boundary and the tail are predicated byte loads and stores.  No workspace, no atomics,
+ * asynchronous on `stream`.
+ * Checked on the host before any device call: DFQ_ERR_INVALID for a NULL d, a, b or out, unknown
+ * flags or non-zero reserved, symmetric not 0 / 1, a_quant or b_quant bits outside 2..8,
+ * out_quant.bits outside {0, 2..8}, a grid with neither a device pointer nor given_max >
+ * given_min (out_quant: only when its bits > 0), n < 1 or above 2^40, a range pointer or an fp32
+ * out not 4-B aligned. */
+typedef struct dfq_int_add_desc {
+    const void*  a;         /* n code bytes on a_quant */
+    const void*  b;         /* n code bytes on b_quant */
+    void*        out;       /* n floats, or n code bytes on out_quant */
+    dfq_int_mbconv_quant a_quant;
+    dfq_int_mbconv_quant b_quant;
+    dfq_int_mbconv_quant out_quant;   /* bits 0: fp32 output */
+    int64_t      n;
+    int32_t      flags;     /* 0 */
+    int32_t      reserved;  /* 0 */
+} dfq_int_add_desc;
+int dfq_int_add_q(const dfq_int_add_desc* d, void* stream);
+
+/* dfq_int_mbconv_res_q: the inverted-residual block with its shortcut added in the epilogue.  The
+ * descriptor is dfq_int_mbconv_q's; a dfq_int_mbconv_res next to it names the grid of the
+ * project's output.  The result is bit for bit
+ *   c3  = dfq_int_mbconv_q(d with out_quant := r->proj_quant)      (code bytes, never stored)
+ *   out = dfq_int_add_q(c3 on proj_quant, d->x on d->x_quant, d->out_quant)
+ * The shortcut is read from LDS, not from global memory: with stride 1, pad 1 and Cin == Cout the
+ * code of x at (b, n, oh, ow) is channel n of the staged footprint's pixel (oh - oh0 + 1,
+ * ow - ow0 + 1).  One kernel body serves both entries; the limits are dfq_int_mbconv_q's.
+ * Checks: dfq_int_mbconv_q's, with its codes and order, then DFQ_ERR_INVALID for a NULL r,
+ * proj_quant.bits outside 2..8, symmetric not 0 / 1, unknown flags or non-zero reserved, a grid
+ * with no range, a range pointer not 4-B aligned; DFQ_ERR_SHAPE unless stride == 1, pad == 1 and
+ * Cin == Cout (x and the output are one tensor shape). */
+typedef struct dfq_int_mbconv_res {
+    dfq_int_mbconv_quant proj_quant;   /* the grid of the project's output: the add's first operand; bits 2..8 */
+    int32_t      flags;     /* 0 */
+    int32_t      reserved;  /* 0 */
+} dfq_int_mbconv_res;
+int dfq_int_mbconv_res_q(const dfq_int_mbconv_desc* d, const dfq_int_mbconv_res* r, void* stream);
+
 /* ---- high-bias absorption (bias_absorption.py:147-197) ------------------
  * c = max(bn_b - N*bn_w, 0) (bn_* = the BN's fake_weight / fake_bias);
  * b2[o] += sum_i (sum_k W2[o,i,k]) * c[g*i2 + i];  b1 -= c;  bn_b -= c.
