@@ -45,6 +45,7 @@ EXPORTS = [
     "dfq_int_gemm_grouped", "dfq_int_linear_grouped", "dfq_int_conv2d_grouped",
     "dfq_int_gemm_q", "dfq_int_linear_q", "dfq_int_conv2d_q", "dfq_int_dwconv2d_q",
     "dfq_int_mbconv_q", "dfq_int_add_q", "dfq_int_mbconv_res_q",
+    "dfq_int_mean_q", "dfq_int_maxpool2d_q",
 ]
 #: entry points only the diagnostics library exports (include/dfq_diag.h)
 DIAG_EXPORTS = ["dfq_probe_stream", "dfq_probe_lds", "dfq_debug_timeline", "dfq_debug_ablate",
@@ -234,6 +235,18 @@ class IntMbconvRes(C.Structure):
     _fields_ = [("proj_quant", IntMbconvQuant), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class IntMeanDesc(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("x_quant", IntMbconvQuant), ("out_quant", IntMbconvQuant),
+                ("rows", C.c_int64), ("plane", C.c_int64), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class IntMaxpool2dDesc(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("x_quant", IntMbconvQuant), ("out_quant", IntMbconvQuant),
+                ("B", C.c_int64), ("C", C.c_int64), ("H", C.c_int64), ("W", C.c_int64), ("KH", C.c_int64), ("KW", C.c_int64),
+                ("stride_h", C.c_int64), ("stride_w", C.c_int64), ("pad_h", C.c_int64), ("pad_w", C.c_int64),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 DFQ_BC_OP_EXPECT, DFQ_BC_OP_APPLY, DFQ_BC_OP_PROPAGATE, DFQ_BC_OP_COPY = 0, 1, 2, 3
 DFQ_BC_APPLY_VEC_SCRATCH = 1
 DFQ_BN_FOLD_ZERO_BIAS = 1
@@ -349,6 +362,8 @@ def load(path: Optional[os.PathLike] = None) -> C.CDLL:
         "dfq_int_mbconv_q": ([C.POINTER(IntMbconvDesc), P], C.c_int),
         "dfq_int_add_q": ([C.POINTER(IntAddDesc), P], C.c_int),
         "dfq_int_mbconv_res_q": ([C.POINTER(IntMbconvDesc), C.POINTER(IntMbconvRes), P], C.c_int),
+        "dfq_int_mean_q": ([C.POINTER(IntMeanDesc), P], C.c_int),
+        "dfq_int_maxpool2d_q": ([C.POINTER(IntMaxpool2dDesc), P], C.c_int),
     }
     diag = {
         "dfq_probe_stream": ([P, P, P, P, I64, I32, P], C.c_int),

@@ -28,6 +28,7 @@ SOURCES = ["dfq_lib.hip", "dfq_sweep.hip", "dfq_sweep_plan.cpp", "dfq_transform.
            "dfq_int_io.hip", "dfq_int_dwconv_io.hip",   # stored activation codes in and out of the integer entries
            "dfq_int_mbconv.hip", "dfq_int_mbconv_plan.cpp",   # the integer inverted-residual block and its planner
            "dfq_int_add.hip", "dfq_int_add_plan.cpp",   # the residual add on stored codes and its planner
+           "dfq_int_pool.hip", "dfq_int_pool_plan.cpp",   # the mean and the max pool on stored codes and their planner
            "dfq_round.hip", "dfq_round_plan.cpp"]   # sum rounding and its planner
 # Diagnostics build (bench.py's ceiling probes, scripts/ A/B runs): the same
 # sources with -DDFQ_DIAGNOSTICS (the sweep's A/B variants and environment
@@ -55,7 +56,8 @@ FLAGS = [
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {"dfq_round.hip": _NO_PACKED_FP32, "dfq_int_group.hip": _NO_PACKED_FP32,
                 "dfq_int_io.hip": _NO_PACKED_FP32, "dfq_int_dwconv_io.hip": _NO_PACKED_FP32,
-                "dfq_int_mbconv.hip": _NO_PACKED_FP32, "dfq_int_add.hip": _NO_PACKED_FP32}
+                "dfq_int_mbconv.hip": _NO_PACKED_FP32, "dfq_int_add.hip": _NO_PACKED_FP32,
+                "dfq_int_pool.hip": _NO_PACKED_FP32}
 # the same without the offload: hipcc takes a .cpp for HIP unless told otherwise
 # (the planner's placement compares doubles: -ffp-contract=off here too)
 HOST_FLAGS = ["-x", "c++"] + [f for f in FLAGS if "offload-arch" not in f and "-fhip-" not in f]

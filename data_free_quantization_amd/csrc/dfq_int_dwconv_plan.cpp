@@ -35,15 +35,20 @@ int dwc_check(const dfq_int_dwconv2d_desc* d, DwcGeom& g, int64_t& grid, unsigne
     const int64_t K = d->KH * d->KW;
     if (K > kDwMaxTaps) return DFQ_ERR_UNSUPPORTED;
     if ((d->flags & DFQ_INT_B_PACK4) && K % 2) return DFQ_ERR_UNSUPPORTED;
+    const DwcWindow w{d->B, d->C, d->H, d->W, d->mult, d->KH, d->KW, d->stride_h, d->stride_w, d->pad_h, d->pad_w, d->dil_h, d->dil_w, OH, OW};
+    return dwc_tiles(w, g, grid);
+}
 
+int dwc_tiles(const DwcWindow& w, DwcGeom& g, int64_t& grid) {
+    const int64_t OH = w.OH, OW = w.OW, K = w.KH * w.KW;
     // the tile: a plane's rows and columns split evenly over the fewest tiles of at most kDwTileH x
     // kDwTileW (whole quads a tile where a row has several), shrunk until one plane's footprint fits the code bytes
     int64_t th = ceil_div(OH, ceil_div(OH, (int64_t)kDwTileH)), tw = ceil_div(OW, ceil_div(OW, (int64_t)kDwTileW));
     if (tw < OW) tw = ceil_div(tw, (int64_t)kDwQuad) * kDwQuad;
     int64_t fh, fw, fwp;
     for (;;) {
-        fh = (th - 1) * d->stride_h + (d->KH - 1) * d->dil_h + 1;
-        fw = (tw - 1) * d->stride_w + (d->KW - 1) * d->dil_w + 1;
+        fh = (th - 1) * w.stride_h + (w.KH - 1) * w.dil_h + 1;
+        fw = (tw - 1) * w.stride_w + (w.KW - 1) * w.dil_w + 1;
         fwp = (fw + 3) / 4 * 4;
         if (fh <= kDwCodeBytes && fwp <= kDwCodeBytes && fh * fwp <= kDwCodeBytes) break;   // factor by factor: no overflow
         if (th == 1 && tw == 1) return DFQ_ERR_UNSUPPORTED;   // one output's footprint does not fit
@@ -51,7 +56,7 @@ int dwc_check(const dfq_int_dwconv2d_desc* d, DwcGeom& g, int64_t& grid, unsigne
         else tw = (tw + 1) / 2;
     }
     const int64_t tiles_h = ceil_div(OH, th), tiles_w = ceil_div(OW, tw), tqw = ceil_div(tw, (int64_t)kDwQuad);
-    const int64_t planes = d->B * d->C, words = ceil_div(K, (int64_t)4);
+    const int64_t planes = w.B * w.C, words = ceil_div(K, (int64_t)4);
     // planes of a workgroup: where a plane is one tile, as many as fill two quads a lane
     int64_t pp = 1;
     if (tiles_h * tiles_w == 1) {
@@ -62,14 +67,14 @@ int dwc_check(const dfq_int_dwconv2d_desc* d, DwcGeom& g, int64_t& grid, unsigne
         if (pp < 1) pp = 1;
     }
     int64_t mc = kDwWeightWords / (pp * words);
-    if (mc > d->mult) mc = d->mult;
+    if (mc > w.mult) mc = w.mult;
     const int64_t n = ceil_div(planes, pp) * tiles_h * tiles_w;
     if (n > 0x7fffffff) return DFQ_ERR_UNSUPPORTED;
 
-    g.C = (int32_t)d->C; g.H = (int32_t)d->H; g.W = (int32_t)d->W; g.mult = (int32_t)d->mult;
-    g.KH = (int32_t)d->KH; g.KW = (int32_t)d->KW; g.OH = (int32_t)OH; g.OW = (int32_t)OW;
-    g.sh = (int32_t)d->stride_h; g.sw = (int32_t)d->stride_w; g.ph = (int32_t)d->pad_h; g.pw = (int32_t)d->pad_w;
-    g.dh = (int32_t)d->dil_h; g.dw = (int32_t)d->dil_w;
+    g.C = (int32_t)w.C; g.H = (int32_t)w.H; g.W = (int32_t)w.W; g.mult = (int32_t)w.mult;
+    g.KH = (int32_t)w.KH; g.KW = (int32_t)w.KW; g.OH = (int32_t)OH; g.OW = (int32_t)OW;
+    g.sh = (int32_t)w.stride_h; g.sw = (int32_t)w.stride_w; g.ph = (int32_t)w.pad_h; g.pw = (int32_t)w.pad_w;
+    g.dh = (int32_t)w.dil_h; g.dw = (int32_t)w.dil_w;
     g.HW = g.H * g.W; g.OHW = g.OH * g.OW;
     g.K = (int32_t)K; g.words = (int32_t)words;
     g.th = (int32_t)th; g.tw = (int32_t)tw; g.tqw = (int32_t)tqw;
@@ -77,7 +82,7 @@ int dwc_check(const dfq_int_dwconv2d_desc* d, DwcGeom& g, int64_t& grid, unsigne
     g.fwords = (int32_t)(fh * fwp / 4);
     g.pp = (int32_t)pp; g.mc = (int32_t)mc;
     g.tiles_h = (int32_t)tiles_h; g.tiles_w = (int32_t)tiles_w;
-    g.masked = (d->pad_h | d->pad_w) != 0;
+    g.masked = (w.pad_h | w.pad_w) != 0;
     g.planes = planes;
     grid = n;
     return DFQ_OK;

@@ -192,5 +192,12 @@ DFQ_HOST_DEVICE inline int64_t dwc_out_offset(const DwcGeom& g, int64_t p, int32
 // dfq_int_dwconv2d's argument checks (no device call): DFQ_OK with the geometry and the grid, or
 // the error.
 int dwc_check(const dfq_int_dwconv2d_desc* d, DwcGeom& g, int64_t& grid, unsigned bytes = 0);   // bytes: kIgBytesX | kIgBytesOut
+// The tile decomposition alone, for a window whose extents have passed their checks (dwc_check's
+// last step; dfq_int_maxpool2d_q tiles its planes the same way): the geometry and the grid, or
+// DFQ_ERR_UNSUPPORTED.
+struct DwcWindow {
+    int64_t B, C, H, W, mult, KH, KW, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, OH, OW;
+};
+int dwc_tiles(const DwcWindow& w, DwcGeom& g, int64_t& grid);
 
 }  // namespace dfq

@@ -16,7 +16,8 @@ elements of a weight row (``group_quant`` writes them; tests/int_group_cases.py)
 activation codes instead of fp32, and the two convolutions read such codes (``x_codes``), so a
 run of layers exchanges uint8 tensors (tests/int_io_cases.py); ``int_mbconv_q`` runs MobileNetV2's
 expand -> depthwise -> project block on such codes in one launch, the hidden tensors in LDS, with the block's residual add in its
-epilogue under ``residual``; ``int_add_q`` adds two code tensors.
+epilogue under ``residual``; ``int_add_q`` adds two code tensors; ``int_mean_q`` and ``int_maxpool2d_q`` are the classifiers'
+global average pool and max pool on such codes.
 There is no CPU fallback: CPU tensors raise."""
 from __future__ import annotations
 
@@ -635,6 +636,90 @@ def int_add_q(a_codes: torch.Tensor, a_quant: OutQuant, b_codes: torch.Tensor, b
     _bias_dev_args("int_add_q", 0, dev, None, (*tensors, b_codes, out))
     d.a, d.b, d.out, d.n = a_codes.data_ptr(), b_codes.data_ptr(), out.data_ptr(), a_codes.numel()
     _lib.check(_lib.load().dfq_int_add_q(C.byref(d), _lib.raw_stream(dev)), "dfq_int_add_q", ValueError)
+    return out
+
+
+def _pool_operand(what: str, d, x_codes, x_quant, out_quant, min_dims: int) -> list:
+    """``x_codes`` of a pooling call and its two grids before any device is looked at: ``_add_operand``'s checks, then the
+    tensor's; the grids' tensors."""
+    tensors: list = []
+    _add_operand("x", x_codes, x_quant, d.x_quant, tensors)
+    if out_quant is not None:
+        _mb_quant(d.out_quant, "out_quant", out_quant, tensors)
+    _on_gpu("x_codes", x_codes, "a uint8 or int8 tensor")
+    if x_codes.dim() < min_dims or not x_codes.is_contiguous() or x_codes.numel() == 0:
+        raise ValueError("%s: x_codes must be a non-empty contiguous tensor of %d dimensions%s, got %s with strides %s"
+                         % (what, min_dims, " or more" if min_dims == 3 else "", tuple(x_codes.shape), tuple(x_codes.stride())))
+    return tensors
+
+
+def int_mean_q(x_codes: torch.Tensor, x_quant: OutQuant, *, out_quant: Optional[OutQuant] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The mean over H * W of a tensor of stored codes in one launch (dfq_int_mean_q; DESIGN.md
+    3.9.4): the classifiers' global average pool, staying on bytes.  ``x_codes``: a contiguous
+    [B, C, H, W] or [B, C, P] tensor (any trailing dimensions) on the GPU, uint8, or int8 when its
+    grid ``x_quant`` (an ``OutQuant``) is symmetric, else TypeError; any byte address is taken.
+    With S the integer sum of a plane's codes and (s, z) ``fake_quant``'s scale and zero of the
+    grid, the result [B, C] is ``float32((float64(s) * S) / P + float64(z))`` -- or, under
+    ``out_quant``, ``fake_quant_given``'s code byte of that value.  The sum is an integer, so the
+    bits do not depend on how the kernel splits the work.  P is at most 2^23, else
+    NotImplementedError.  ``out``, if passed, is a contiguous [B, C] tensor of the result's type.
+    Asynchronous on the current stream; there is no CPU fallback."""
+    d = _lib.IntMeanDesc()
+    tensors = _pool_operand("int_mean_q", d, x_codes, x_quant, out_quant, 3)
+    dev, shape = x_codes.device, tuple(x_codes.shape[:2])
+    if out_quant is not None:
+        out = _code_out("int_mean_q", shape, out, out_quant, dev)
+    elif out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32:
+        raise TypeError("out: float32 on the GPU")
+    elif tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError("out must be a contiguous %s tensor" % (list(shape),))
+    _bias_dev_args("int_mean_q", 0, dev, None, (*tensors, out))
+    d.x, d.out, d.rows = x_codes.data_ptr(), out.data_ptr(), shape[0] * shape[1]
+    d.plane = x_codes.numel() // d.rows
+    _lib.check(_lib.load().dfq_int_mean_q(C.byref(d), _lib.raw_stream(dev)), "dfq_int_mean_q", ValueError)
+    return out
+
+
+def int_maxpool2d_q(x_codes: torch.Tensor, x_quant: OutQuant, kernel_size, stride=None, padding=0, *,
+                    out_quant: Optional[OutQuant] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``F.max_pool2d`` (dilation 1, ceil mode off) on stored codes in one launch
+    (dfq_int_maxpool2d_q).  ``x_codes``: a contiguous [B, C, H, W] tensor on the
+    GPU, uint8, or int8 when its grid ``x_quant`` (an ``OutQuant``) is symmetric, else TypeError.
+    The result [B, C, OH, OW] holds the largest code -- as the grid's integers -- among each
+    window's taps inside the image: with a positive scale that is ``F.max_pool2d`` of the
+    dequantized tensor, on the same grid, with no arithmetic at all.  A padding tap is absent, not
+    a zero byte.  Under ``out_quant`` the maximum's fp32 value on ``x_quant`` is requantized to
+    ``fake_quant_given``'s code byte on that grid.  ``kernel_size``, ``stride``, ``padding``: ints
+    or (h, w) pairs; ``stride=None`` is the kernel size and ``padding`` is at most half the kernel,
+    as in torch, else ValueError.  KH * KW is at most ``DW_MAX_TAPS``.  ``out``, if passed, is a
+    contiguous byte tensor of the result's shape and type.  Asynchronous on the current stream;
+    there is no CPU fallback."""
+    (KH, KW), (ph, pw) = mx._pair(kernel_size, "kernel_size"), mx._pair(padding, "padding")
+    sh, sw = (KH, KW) if stride is None else mx._pair(stride, "stride")
+    if min(KH, KW, sh, sw) < 1 or min(ph, pw) < 0:
+        raise ValueError("kernel_size and stride must be >= 1 and padding >= 0")
+    if ph > KH // 2 or pw > KW // 2:
+        raise ValueError("padding %s must be at most half the kernel %s" % ((ph, pw), (KH, KW)))
+    if KH * KW > DW_MAX_TAPS:
+        raise NotImplementedError("KH * KW must be <= %d, got %d" % (DW_MAX_TAPS, KH * KW))
+    d = _lib.IntMaxpool2dDesc()
+    tensors = _pool_operand("int_maxpool2d_q", d, x_codes, x_quant, out_quant, 4)
+    if x_codes.dim() != 4:
+        raise ValueError("int_maxpool2d_q: x_codes must be [B, C, H, W], got %s" % (tuple(x_codes.shape),))
+    B, Cn, H, W = x_codes.shape
+    OH, OW = mx.conv_out_size(H, KH, sh, ph, 1), mx.conv_out_size(W, KW, sw, pw, 1)
+    if OH < 1 or OW < 1:
+        raise ValueError("the kernel %s does not fit the padded input %s" % ((KH, KW), (H + 2 * ph, W + 2 * pw)))
+    dev = x_codes.device
+    out = _code_out("int_maxpool2d_q", (B, Cn, OH, OW), out, out_quant if out_quant is not None else x_quant, dev)
+    _bias_dev_args("int_maxpool2d_q", 0, dev, None, (*tensors, out))
+    d.x, d.out = x_codes.data_ptr(), out.data_ptr()
+    d.B, d.C, d.H, d.W, d.KH, d.KW = B, Cn, H, W, KH, KW
+    d.stride_h, d.stride_w, d.pad_h, d.pad_w = sh, sw, ph, pw
+    _lib.check(_lib.load().dfq_int_maxpool2d_q(C.byref(d), _lib.raw_stream(dev)), "dfq_int_maxpool2d_q", ValueError)
     return out
 
 

@@ -1177,6 +1177,80 @@ typedef struct dfq_int_mbconv_res {
 } dfq_int_mbconv_res;
 int dfq_int_mbconv_res_q(const dfq_int_mbconv_desc* d, const dfq_int_mbconv_res* r, void* stream);
 
+/* ---- pooling on stored codes (no reference counterpart) ----
+ * dfq_int_mean_q: the mean over a plane of a tensor of codes in one launch -- the classifiers'
+ * global average pool.  x is `rows` (B * C) contiguous rows of `plane` (H * W) code bytes on
+ * x_quant (uint8, or int8 when the grid is symmetric; 1-B aligned).  With q the stored byte's
+ * integer and (s, z) the fp32 step and offset of x_quant's range (make_qparams'),
+ *   S_r = sum_i q[r, i]                                   (an exact integer)
+ *   m   = (double(s) * double(S_r)) / double(plane) + double(z)    (each operation rounded once)
+ *   y_r = float(m);   out[r] = y_r   (out_quant.bits == 0: fp32, 4-B aligned)
+ *                     out[r] = q_O(y_r)   (bits 2..8: dfq_fake_quant_given's code byte on out_quant)
+ * S is an integer sum, so the result is the statement's bits whatever the split.
+ * Planes of up to 4096 bytes: a workgroup owns a run of consecutive rows, its lanes take the 16-B
+ * chunks of the run counted from its first 16-B boundary, cut each chunk at the row boundaries
+ * inside it and add the pieces' sums (the packed 8-bit dot instruction against a word of ones)
+ * into one int32 a row in LDS.  Larger planes: a workgroup a row, a wave reduction, then LDS.  One
+ * lane a row runs the fp64 epilogue; four rows' codes go out as one word where the address allows.
+ * No byte outside x is read.  No workspace, no global atomics, asynchronous on `stream`.
+ * Checked on the host before any device call: DFQ_ERR_INVALID for a NULL d, x or out, unknown flags
+ * or non-zero reserved, symmetric not 0 / 1, x_quant.bits outside 2..8, out_quant.bits outside
+ * {0, 2..8}, a grid with neither a device pointer nor given_max > given_min (out_quant: only when
+ * its bits > 0), rows or plane < 1, rows * plane above 2^40, a range pointer or an fp32 out not 4-B
+ * aligned; DFQ_ERR_UNSUPPORTED for plane above 2^23 (the sum stays inside int32) or a grid beyond
+ * int32. */
+typedef struct dfq_int_mean_desc {
+    const void*  x;         /* rows * plane code bytes on x_quant */
+    void*        out;       /* rows floats, or rows code bytes on out_quant */
+    dfq_int_mbconv_quant x_quant;
+    dfq_int_mbconv_quant out_quant;   /* bits 0: fp32 output */
+    int64_t      rows;      /* B * C */
+    int64_t      plane;     /* H * W */
+    int32_t      flags;     /* 0 */
+    int32_t      reserved;  /* 0 */
+} dfq_int_mean_desc;
+int dfq_int_mean_q(const dfq_int_mean_desc* d, void* stream);
+
+/* dfq_int_maxpool2d_q: max pooling on codes in one launch (dilation 1, ceil mode off).  x is code
+ * bytes [B, C, H, W], contiguous, on x_quant; the output is code bytes [B, C, OH, OW],
+ * OH = (H + 2 pad_h - KH) / stride_h + 1 rounded down.
+ *   c   = the maximum, as the grid's integers (unsigned for uint8, signed for int8), over the
+ *         window's taps that lie inside the image
+ *   out = c                                  (out_quant.bits == 0: the output is on x_quant)
+ *   out = q_O(fl32(fl32(c * s) + z))         (bits 2..8: c's fp32 value on x_quant, requantized)
+ * A padding tap is absent, never a byte of some value.  With s > 0 a code's value does not
+ * decrease in the code, so the first form is F.max_pool2d of the dequantized tensor on its grid.
+ * The tiles are dfq_int_dwconv2d's: a workgroup stages the input footprint of its tile -- of
+ * several planes where a plane is one tile -- once into LDS as words, a lane produces four
+ * consecutive ow of one output row, first along KW, then along KH, under the row and column tap
+ * masks, and stores them as one word where the address allows.  No workspace, no atomics,
+ * asynchronous on `stream`.
+ * Checked on the host before any device call: DFQ_ERR_INVALID for a NULL d, x or out, unknown
+ * flags or non-zero reserved, the grids' checks as above, an extent (B, C, H, W, KH, KW) or stride
+ * < 1, pad < 0, any of these above 2^28, pad_h > KH / 2 or pad_w > KW / 2, H * W or OH * OW at or
+ * above 2^31, a range pointer not 4-B aligned; DFQ_ERR_SHAPE when OH or OW comes out < 1;
+ * DFQ_ERR_UNSUPPORTED for KH * KW > DFQ_INT_DW_MAX_TAPS, a footprint beyond DFQ_INT_DW_LDS_BYTES,
+ * a grid beyond int32. */
+typedef struct dfq_int_maxpool2d_desc {
+    const void*  x;         /* code bytes [B, C, H, W] on x_quant */
+    void*        out;       /* code bytes [B, C, OH, OW] */
+    dfq_int_mbconv_quant x_quant;
+    dfq_int_mbconv_quant out_quant;   /* bits 0: the output stays on x_quant */
+    int64_t      B;
+    int64_t      C;
+    int64_t      H;
+    int64_t      W;
+    int64_t      KH;
+    int64_t      KW;
+    int64_t      stride_h;
+    int64_t      stride_w;
+    int64_t      pad_h;
+    int64_t      pad_w;
+    int32_t      flags;     /* 0 */
+    int32_t      reserved;  /* 0 */
+} dfq_int_maxpool2d_desc;
+int dfq_int_maxpool2d_q(const dfq_int_maxpool2d_desc* d, void* stream);
+
 /* ---- high-bias absorption (bias_absorption.py:147-197) ------------------
  * c = max(bn_b - N*bn_w, 0) (bn_* = the BN's fake_weight / fake_bias);
  * b2[o] += sum_i (sum_k W2[o,i,k]) * c[g*i2 + i];  b1 -= c;  bn_b -= c.
